@@ -19,7 +19,14 @@ between density and force refreshes the halo's rho point-to-point
 includes that exchange. --scaling weak: N unit cubes along x, one x-slab per
 rank, no exchange.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does what the headline needs and no more: setup, warm-up, the
+timed steps, one JSON line. --full adds everything else the line can carry
+(CPU baselines, parity legs, steady state, step breakdown, the other BASELINE
+configs, the cosmo step's per-family times); the --no-* options trim a --full
+run. --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        torchrun ... bench.py --gpus N   (one process per GPU)
 """
 from __future__ import annotations
@@ -686,6 +693,60 @@ def load_traffic(workload="sedov"):
     return None
 
 
+DUMP_SEED = 20240611       # the sample of a large output: fixed, so two builds compare
+DUMP_MAX_ROWS = 1 << 19    # rows kept per array (<= 64 MB over every array of a workload)
+HYDRO_DENSITY_OUT = ("rho", "rho_dh", "wcount", "wcount_dh", "div_v", "rot_v")
+HYDRO_FORCE_OUT = ("a_hydro", "u_dt", "h_dt")
+GRAV_OUT = ("a_grav", "potential")
+
+
+def dump_rows(n):
+    """Row indices written by --dump-outputs for an n-row output: all of them,
+    or a sorted seeded sample of DUMP_MAX_ROWS."""
+    if n <= DUMP_MAX_ROWS:
+        return np.arange(n)
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    return np.sort(rng.choice(n, DUMP_MAX_ROWS, replace=False))
+
+
+def dump_arrays(outdir, arrays, rank, world):
+    """DIR/<name>.npy (float32, ids float64); <name>.rank<k>.npy with N ranks."""
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype.itemsize == 8 else np.float32)
+        np.save(os.path.join(outdir, name + (f".rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
+def hydro_outputs(sp, local, n_owned, prefix=""):
+    """What a caller of the timed density + force loops receives: the density
+    loop's sums and the force loop's rates of the owned particles, downloaded
+    from the space as it stands after the last step."""
+    from swift_subtask_dev_amd import abi
+
+    rows = dump_rows(n_owned)
+    out = {prefix + "id": local["id"][:n_owned][rows].astype(np.float64)}
+    for fields, names in ((abi.FIELDS_DENSITY, HYDRO_DENSITY_OUT),
+                          (abi.FIELDS_FORCE, HYDRO_FORCE_OUT)):
+        got = abi.copy_parts(local)
+        sp.download(got, fields)
+        for f in names:
+            out[prefix + f] = got[f][:n_owned][rows]
+    return out
+
+
+def grav_outputs(gs, gparts, names, prefix=""):
+    """The gravity outputs of every gpart after the last step."""
+    from swift_subtask_dev_amd import abi
+
+    rows = dump_rows(len(gparts))
+    got = abi.copy_parts(gparts)
+    gs.download(got)
+    out = {prefix + "id": got["id_or_neg_offset"][rows].astype(np.float64)}
+    for f in names:
+        out[prefix + f] = got[f][rows]
+    return out
+
+
 def run_grav(args, ctx, rank, world, dist, torch):
     """BASELINE config 4: GravityTests uniform DM box, P2P leaf interactions
     (runner_doself_grav_pp + runner_dopair_grav_pp over each leaf and its 26
@@ -734,6 +795,8 @@ def run_grav(args, ctx, rank, world, dist, torch):
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
+    if args.dump_outputs:
+        dump_arrays(args.dump_outputs, grav_outputs(sp, gs, GRAV_OUT), rank, world)
     tot = torch.tensor([float(n_int) * args.steps], dtype=torch.float64, device=RED_DEVICE)
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=RED_DEVICE)
     if dist:
@@ -948,7 +1011,14 @@ def run_cosmo(args, ctx, rank, world, dist, torch):
             el = x.item()
         return el / args.steps
 
-    t_h, t_g, t_b = timed(hydro), timed(gravity), timed(both)
+    # each family alone takes timed runs of its own: --full only
+    t_h, t_g = (timed(hydro), timed(gravity)) if args.full else (None, None)
+    t_b = timed(both)
+    if args.dump_outputs:
+        arrays = hydro_outputs(hs, local, n_owned, "gas_")
+        arrays.update(grav_outputs(gs, g, ("a_grav", "a_grav_mesh", "potential", "potential_mesh"),
+                                   "gpart_"))
+        dump_arrays(args.dump_outputs, arrays, rank, world)
     mine = [float(n_density + n_force + stats["n_pp"]), float(n_density + n_force),
             float(stats["n_pp"])]
     tot = torch.tensor(mine, dtype=torch.float64, device=RED_DEVICE)
@@ -956,9 +1026,12 @@ def run_cosmo(args, ctx, rank, world, dist, torch):
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
     total, total_hydro, total_pp = tot.tolist()
     # roofline: the step's dominant kernel is the gravity P2P (its own HIP
-    # events inside swh_grav_tree, on the gravity stream)
-    st = gs.tree(G, tops, pairs)
-    gs.sync()
+    # events inside swh_grav_tree, on the gravity stream): a walk of its own,
+    # --full only
+    st = None
+    if args.full:
+        st = gs.tree(G, tops, pairs)
+        gs.sync()
     if rank == 0:
         out = {
             "metric": "hydro (density+force) + gravity P2P interactions/s, SmallCosmoVolume stand-in",
@@ -984,13 +1057,15 @@ def run_cosmo(args, ctx, rank, world, dist, torch):
                        "gravity_pp_per_step": int(total_pp),
                        "gravity_tree_stats_rank0": stats, "cells": int(len(cells)),
                        "softening": eps, "r_s": r_s},
-            "step_ms": {"hydro_alone": t_h * 1e3, "gravity_alone": t_g * 1e3,
+            "step_ms": {"hydro_alone": t_h * 1e3 if args.full else None,
+                        "gravity_alone": t_g * 1e3 if args.full else None,
                         "overlapped": t_b * 1e3,
-                        "overlap_gain": (t_h + t_g) / t_b, "overlap_mode": overlap},
-            "gravity_phase_ms_rank0": st["ms"],
+                        "overlap_gain": (t_h + t_g) / t_b if args.full else None,
+                        "overlap_mode": overlap},
+            "gravity_phase_ms_rank0": st["ms"] if st else None,
             "roofline": None, "cpu_baseline": None,
         }
-        t_p2p = st["ms"]["p2p"] * 1e-3
+        t_p2p = st["ms"]["p2p"] * 1e-3 if st else 0.0
         if t_p2p > 0:
             # 28 flops per Newtonian pair, 43 per truncated pair
             n_tr = st["n_pp_truncated"]
@@ -1040,8 +1115,8 @@ def run_cosmo(args, ctx, rank, world, dist, torch):
     gs.close()
 
 
-# BASELINE.json configs 3-5, run after the headline by the default 1-GPU
-# bench (bench.py --workload ...): each child prints one JSON line with its
+# BASELINE.json configs 3-5, run after the headline by a --full 1-GPU
+# bench (bench.py --workload ... --full): each child prints one JSON line with its
 # own value, ms_per_step, roofline (the PMC traffic named by commit) and
 # cpu_baseline
 OTHER_CONFIGS = {
@@ -1057,7 +1132,7 @@ def other_configs(args):
     res = {}
     for name, extra in OTHER_CONFIGS.items():
         cmd = [sys.executable, str(Path(__file__).resolve()), *extra, "--steps", str(args.steps),
-               "--warmup", str(args.warmup), "--no-configs"]
+               "--warmup", str(args.warmup), "--full", "--no-configs"]
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
         t0 = time.perf_counter()
@@ -1098,6 +1173,15 @@ def main():
                          "SWH_DEFAULT_LIST_SKIN = 0.01)")
     ap.add_argument("--list-capacity", type=int, default=0, help="pair-list entries per particle")
     ap.add_argument("--precision", default="f64", choices=["f64", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else the line "
+                         "can carry: CPU baselines, parity against the CPU port, steady state, "
+                         "full-step breakdown, the BASELINE configs 3-5, the cosmo step's hydro and "
+                         "gravity alone and its P2P roofline (the --no-* options trim this)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (the loops' "
+                         "output fields of the owned particles; a fixed seeded sample of at most "
+                         f"{DUMP_MAX_ROWS} rows per array) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-runs", type=int, default=3)
     ap.add_argument("--no-steady", action="store_true", help="skip the untimed steady-state run")
@@ -1110,7 +1194,7 @@ def main():
     ap.add_argument("--no-breakdown", action="store_true",
                     help="skip the untimed full-step breakdown (drift, rebuild, chain)")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the BASELINE configs 3-5 lines the default 1-GPU run appends "
+                    help="skip the BASELINE configs 3-5 lines a --full 1-GPU run appends "
                          "(each a child bench.py run, untimed by the headline)")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="strong: the 128^3 box split over the GPUs (the metric); "
@@ -1127,6 +1211,8 @@ def main():
     if args.cpu_worker:  # child of run_cpu_worker: no torch, no GPU
         cpu_worker_main(args.cpu_worker, args.cpu_input, json.loads(args.cpu_meta))
         return
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_steady = args.no_breakdown = args.no_configs = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N`: one rank per GPU under torch.distributed.run,
@@ -1293,6 +1379,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_arrays(args.dump_outputs, hydro_outputs(sp, local, n_owned), rank, world)
     t_dens = [e[0].elapsed_time(e[1]) * 1e-3 for e in events]
     t_force = [e[2].elapsed_time(e[3]) * 1e-3 for e in events]
     # the halo refresh of rho (pack, point-to-point swap, unpack) per rank
