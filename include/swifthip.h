@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define SWH_ABI_VERSION 11
+#define SWH_ABI_VERSION 12
 
 #if defined(__GNUC__)
 #define SWH_API __attribute__((visibility("default")))
@@ -89,11 +89,13 @@ typedef struct swh_part_layout {
   int32_t off_gpart;            /* struct gpart* (drift: gravity kick if non-NULL), -1: none */
 } swh_part_layout;
 
-/* struct xpart fields the drift reads (src/hydro/SPHENIX/hydro_part.h:50-90). */
+/* struct xpart fields the drift and the kicks read and write
+ * (src/hydro/SPHENIX/hydro_part.h:50-90). */
 typedef struct swh_xpart_layout {
   int32_t stride;     /* sizeof(struct xpart) */
   int32_t off_v_full; /* float[3] */
   int32_t off_a_grav; /* float[3] */
+  int32_t off_u_full; /* float; -1: absent (no kick / timestep then) -- ABI v12 */
 } swh_xpart_layout;
 
 typedef struct swh_gpart_layout {
@@ -279,6 +281,8 @@ SWH_API swh_status swh_space_upload_parts(swh_space *s, const void *parts, int64
 #define SWH_FIELDS_FORCE 4
 #define SWH_FIELDS_DRIFT 8
 #define SWH_FIELDS_ALL 15
+/* time_bin, as swh_space_timestep chose it (ABI v12; not part of ALL) */
+#define SWH_FIELDS_TIMEBIN 16
 SWH_API swh_status swh_space_download_parts(swh_space *s, void *parts, const swh_part_layout *L,
                                     int fields, int on_device);
 SWH_API int64_t swh_space_count(const swh_space *s);
@@ -333,7 +337,9 @@ SWH_API swh_status swh_space_unpack_halo(swh_space *s, const int32_t *idx, int32
  * widen their reach by the largest displacement since the last rebuild
  * (swh_space_info.dx_max, SWIFT's dx_max_part), so they stay exact; rebuild
  * when it grows too large (SWIFT: space_maxreldx of the cell size). The
- * xparts (v_full, a_grav) are uploaded in caller order, once per step. */
+ * xparts (v_full, a_grav, u_full) are uploaded in caller order: once per step
+ * by a caller that kicks on the host, once at the start by one that uses the
+ * device kicks below. */
 typedef struct swh_drift_params {
   double dt_drift, dt_kick_hydro, dt_kick_grav, dt_therm;
   float min_u; /* hydro_props->minimal_internal_energy / cosmo->a_factor_internal_energy */
@@ -342,6 +348,113 @@ SWH_API swh_status swh_space_upload_xparts(swh_space *s, const void *xparts, int
                                            const swh_xpart_layout *XL, int on_device);
 SWH_API swh_status swh_space_drift(swh_space *s, const swh_drift_params *D,
                                    const swh_hydro_params *P);
+
+/* ------------------------------------------------------------------ */
+/* Time integration on the device (ABI v12): the three per-particle    */
+/* tasks between runner_do_end_hydro_force and the next drift.         */
+/*   swh_space_kick2    runner_do_kick2 for parts                      */
+/*                      (src/runner_time_integration.c:359-465):       */
+/*                      kick_part + hydro_kick_extra over the second   */
+/*                      half of the particle's step, then              */
+/*                      hydro_reset_predicted_values                   */
+/*   swh_space_timestep runner_do_timestep for parts (:637-838):       */
+/*                      get_part_timestep + make_integer_timestep, the */
+/*                      new time_bin, and the next synchronisation     */
+/*                      point of the whole set                         */
+/*   swh_space_kick1    runner_do_kick1 for parts (:87-200): the first */
+/*                      half of the (new) step, no reset               */
+/*   swh_space_end_step the three above in one launch and one pass     */
+/* All run the same per-particle device code, on the owned, not        */
+/* inhibited particles with time_bin <= max_active_bin (kick2 and      */
+/* timestep: part_is_active; kick1: part_is_starting on the new bin);  */
+/* foreign halo copies and inhibited particles are never touched. They */
+/* only enqueue on the space's stream. v_full, u_full and a_grav live  */
+/* on the device from swh_space_upload_xparts on: the kicks advance    */
+/* them there and a rebuild carries them through the re-sort.          */
+/* a_grav is the total gravitational acceleration the caller uploaded  */
+/* (tree + mesh): there is no separate mesh kick (a_grav_mesh,         */
+/* dt_kick_mesh_grav); the caller that integrates the mesh on its own  */
+/* schedule adds it to a_grav for the kicks where it applies.          */
+/* Entropy and pressure floors NONE, as the drift.                     */
+/* ------------------------------------------------------------------ */
+typedef struct swh_kick_params {
+  int64_t ti_current;     /* e->ti_current */
+  double time_base;       /* e->time_base  */
+  int32_t max_active_bin; /* e->max_active_bin */
+  float min_u;            /* as swh_drift_params.min_u */
+  /* Half-step of every time bin b (SWH_NUM_TIME_BINS + 1 entries each,
+   * nullable, as swh_hydro_params.dt_alpha_bins). NULL: non-cosmological,
+   * (get_integer_timestep(b) / 2) * time_base. With cosmology the engine
+   * fills them from kick_get_hydro_kick_dt / kick_get_grav_kick_dt /
+   * kick_get_therm_kick_dt (src/kick.h:46-135) over the half the call
+   * integrates: kick2's [ti_current - ti_step / 2, ti_current], kick1's
+   * [ti_current, ti_current + ti_step / 2]; the two differ, so each call
+   * gets its own tables. */
+  const double *dt_kick_hydro;
+  const double *dt_kick_grav;
+  const double *dt_kick_therm;
+} swh_kick_params;
+
+/* hydro_props / cosmology / engine scalars of get_part_timestep
+ * (src/timestep.h:141-222); a and a_factor_sound_speed come from the
+ * swh_hydro_params of the call. */
+typedef struct swh_timestep_params {
+  float CFL_condition;           /* hydro_props->CFL_condition */
+  float log_max_h_change;        /* hydro_props->log_max_h_change */
+  double dt_min, dt_max;         /* e->dt_min, e->dt_max */
+  float dt_max_RMS_displacement; /* e->dt_max_RMS_displacement (FLT_MAX: off) */
+  /* gravity_compute_timestep_self (gravity/MultiSoftening/gravity.h:141-170)
+   * for particles with a gpart: 2 kernel_gravity_softening_plummer_equivalent_inv
+   * a eta epsilon_gas, dt = sqrt(grav_dt_factor / |a_phys|); <= 0: no gravity
+   * condition */
+  float grav_dt_factor;
+  double time_step_factor;       /* cosmo->time_step_factor (1: off) */
+  double time_base_inv;          /* e->time_base_inv */
+  int64_t ti_current;            /* e->ti_current */
+  double a_factor_grav_accel, a_factor_hydro_accel; /* cosmology */
+} swh_timestep_params;
+
+/* Record of the last swh_space_timestep / swh_space_end_step, over the
+ * owned, not inhibited particles (active or not), as runner_do_timestep
+ * collects it for a cell (:759-764, :789-804). */
+typedef struct swh_step_result {
+  int64_t ti_end_min, ti_end_max, ti_beg_max;
+  int64_t n_updated;      /* particles that got a new time step */
+  int64_t n_below_dt_min; /* of them: wanted a step below dt_min (clamped) */
+  float vfull_max;        /* max |v_full| after the last kick */
+  int32_t reserved;
+} swh_step_result;
+
+SWH_API swh_status swh_space_kick1(swh_space *s, const swh_kick_params *K,
+                                   const swh_hydro_params *P);
+SWH_API swh_status swh_space_kick2(swh_space *s, const swh_kick_params *K,
+                                   const swh_hydro_params *P);
+/* Particles with time_bin <= P->max_active_bin get their new bin. Kept pair
+ * lists (swh_tuning.list_keep) are dropped: they hold the active particles of
+ * the bins they were built with. */
+SWH_API swh_status swh_space_timestep(swh_space *s, const swh_timestep_params *T,
+                                      const swh_hydro_params *P);
+SWH_API swh_status swh_space_end_step(swh_space *s, const swh_kick_params *K2,
+                                      const swh_timestep_params *T, const swh_kick_params *K1,
+                                      const swh_hydro_params *P);
+/* Waits for the last swh_space_timestep / swh_space_end_step (and the kicks
+ * queued after it) and returns its record, which the kernel's launch copies
+ * into pinned host memory behind it. SWH_ERR_STATE when none was queued since
+ * the last upload. SWH_ERR_ARG (the record is still returned) when
+ * n_below_dt_min > 0: SWIFT error()s there (src/timestep.h:202-204).
+ * Every kick measures max |v_full|; the next swh_space_drift bounds its
+ * displacement with it and waits for the record if the caller has not fetched
+ * it: this is a device-resident step's one host synchronisation (the caller
+ * needs ti_end_min there anyway, to choose the next ti_current). */
+SWH_API swh_status swh_space_step_result(swh_space *s, swh_step_result *out);
+/* v_full and u_full (caller order) into the caller's struct xpart records
+ * (the other bytes of the records stay as they are). */
+SWH_API swh_status swh_space_download_xparts(swh_space *s, void *xparts,
+                                             const swh_xpart_layout *XL, int on_device);
+/* Replace the device copy of xp->a_grav (n x 3 floats, caller order) without
+ * touching v_full / u_full: the gravity side delivers a new acceleration every
+ * step, and re-uploading whole xparts would overwrite the kicked v_full. */
+SWH_API swh_status swh_space_upload_a_grav(swh_space *s, const float *a_grav, int on_device);
 
 /* Wait for all queued work on the space's stream. */
 SWH_API swh_status swh_space_sync(swh_space *s);

@@ -97,7 +97,7 @@ XPART_DTYPE = np.dtype(
 )
 
 # include/swifthip.h SWH_ABI_VERSION: the ctypes layouts below are written for it
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 NUM_TIME_BINS = 56  # src/timeline.h:36
 TIME_BIN_INHIBITED = NUM_TIME_BINS + 2
@@ -137,7 +137,85 @@ class PartLayout(C.Structure):
 
 
 class XPartLayout(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("stride", "off_v_full", "off_a_grav")]
+    """swh_xpart_layout; off_u_full (ABI v12) is -1 (absent) unless given."""
+
+    _fields_ = [(n, C.c_int32) for n in ("stride", "off_v_full", "off_a_grav", "off_u_full")]
+
+    def __init__(self, stride=0, off_v_full=0, off_a_grav=-1, off_u_full=-1):
+        super().__init__(stride, off_v_full, off_a_grav, off_u_full)
+
+
+def xpart_layout() -> XPartLayout:
+    """The layout of XPART_DTYPE."""
+    f = XPART_DTYPE.fields
+    return XPartLayout(XPART_DTYPE.itemsize, f["v_full"][1], f["a_grav"][1], f["u_full"][1])
+
+
+def _bin_table(table):
+    if table is None:
+        return None, None
+    arr = (C.c_double * (NUM_TIME_BINS + 1))(*[float(v) for v in table])
+    return arr, C.cast(arr, C.POINTER(C.c_double))
+
+
+class KickParams(C.Structure):
+    """swh_kick_params: one half-kick (kick1 and kick2 get their own)."""
+
+    _fields_ = [("ti_current", C.c_int64), ("time_base", C.c_double),
+                ("max_active_bin", C.c_int32), ("min_u", C.c_float),
+                ("dt_kick_hydro", C.POINTER(C.c_double)),
+                ("dt_kick_grav", C.POINTER(C.c_double)),
+                ("dt_kick_therm", C.POINTER(C.c_double))]
+
+    def set_tables(self, hydro=None, grav=None, therm=None) -> None:
+        """Per-time-bin half-steps (cosmological runs, cosmo.kick_tables);
+        None: the non-cosmological (ti_step / 2) * time_base. The arrays are
+        kept alive by this object."""
+        self._keep = []
+        for name, tab in (("dt_kick_hydro", hydro), ("dt_kick_grav", grav),
+                          ("dt_kick_therm", therm)):
+            arr, ptr = _bin_table(tab)
+            self._keep.append(arr)
+            setattr(self, name, ptr)
+
+
+class TimestepParams(C.Structure):
+    """swh_timestep_params."""
+
+    _fields_ = [("CFL_condition", C.c_float), ("log_max_h_change", C.c_float),
+                ("dt_min", C.c_double), ("dt_max", C.c_double),
+                ("dt_max_RMS_displacement", C.c_float), ("grav_dt_factor", C.c_float),
+                ("time_step_factor", C.c_double), ("time_base_inv", C.c_double),
+                ("ti_current", C.c_int64), ("a_factor_grav_accel", C.c_double),
+                ("a_factor_hydro_accel", C.c_double)]
+
+
+def default_timestep_params(**kw) -> TimestepParams:
+    """SWIFT's defaults (hydro_props_init: CFL 0.1 is the examples' choice,
+    max volume change 1.4 -> log_max_h_change = log(1.4^(1/3))); no
+    displacement, cosmology or gravity condition."""
+    T = TimestepParams()
+    T.CFL_condition = 0.1
+    T.log_max_h_change = float(np.log(1.4 ** (1.0 / 3.0)))
+    T.dt_min, T.dt_max = 0.0, float(np.finfo(np.float32).max)
+    T.dt_max_RMS_displacement = np.finfo(np.float32).max
+    T.grav_dt_factor = 0.0
+    T.time_step_factor = 1.0
+    T.time_base_inv = 0.0
+    T.ti_current = 0
+    T.a_factor_grav_accel = 1.0
+    T.a_factor_hydro_accel = 1.0
+    for k, v in kw.items():
+        setattr(T, k, v)
+    return T
+
+
+class StepResult(C.Structure):
+    """swh_step_result."""
+
+    _fields_ = [("ti_end_min", C.c_int64), ("ti_end_max", C.c_int64), ("ti_beg_max", C.c_int64),
+                ("n_updated", C.c_int64), ("n_below_dt_min", C.c_int64),
+                ("vfull_max", C.c_float), ("reserved", C.c_int32)]
 
 
 class DriftParams(C.Structure):
@@ -285,6 +363,7 @@ LEAF_DTYPE = np.dtype([("start", "<i4"), ("count", "<i4")])
 LEAF_PAIR_DTYPE = np.dtype([("j", "<i4"), ("truncated", "<i4"), ("allow_mpole", "<i4")])
 
 FIELDS_DENSITY, FIELDS_GRADIENT, FIELDS_FORCE, FIELDS_DRIFT, FIELDS_ALL = 1, 2, 4, 8, 15
+FIELDS_TIMEBIN = 16  # time_bin as swh_space_timestep chose it (not part of ALL)
 # halo record fields (swh_space_unpack_halo): h, rho, P + c, f + balsara, alphas
 HALO_H, HALO_RHO, HALO_PC, HALO_F_BALSARA, HALO_ALPHAS, HALO_ALL = 1, 2, 4, 8, 16, 31
 HALO_RECORD_FLOATS = 8

@@ -137,6 +137,36 @@ def dt_alpha_table(cosmo: Cosmology, ti_current: int) -> np.ndarray:
     return out
 
 
+def _kick_integral(cosmo: Cosmology, ti_beg: int, ti_end: int, power: float) -> float:
+    """int dt / a^power over [ti_beg, ti_end] = int dlog(a) / (H a^power): a
+    32-point Gauss-Legendre rule on the interval (SWIFT interpolates tables of
+    the same integrals, cosmology.c:308-402, 636-720)."""
+    lo = cosmo.log_a_begin + ti_beg * cosmo.time_base
+    hi = cosmo.log_a_begin + ti_end * cosmo.time_base
+    xg, wg = np.polynomial.legendre.leggauss(32)
+    a = np.exp(lo + 0.5 * (hi - lo) * (xg + 1.0))
+    return float((0.5 * (hi - lo) * wg / (cosmo.H(a) * a ** power)).sum())
+
+
+def kick_tables(cosmo: Cosmology, ti_current: int, kick: int) -> dict:
+    """swh_kick_params' per-bin half-steps at ti_current with cosmology
+    (kick_get_hydro_kick_dt / _grav_ / _therm_, src/kick.h:46-102): for every
+    bin the second half of the step that ends at ti_current (kick=2,
+    runner_do_kick2) or the first half of the step that starts there (kick=1,
+    runner_do_kick1). Integrands (cosmology.c:308-402): gravity dt / a, hydro
+    dt / a^(3 (gamma - 1)), thermal (the drift factor) dt / a^2."""
+    out = {k: np.zeros(NUM_TIME_BINS + 1) for k in ("hydro", "grav", "therm")}
+    for b in range(1, NUM_TIME_BINS + 1):
+        half = get_integer_timestep(b) // 2
+        lo, hi = (ti_current - half, ti_current) if kick == 2 else (ti_current, ti_current + half)
+        if lo < 0 or hi > MAX_NR_TIMESTEPS:
+            continue  # no such step on the time line
+        out["grav"][b] = _kick_integral(cosmo, lo, hi, 1.0)
+        out["hydro"][b] = _kick_integral(cosmo, lo, hi, 3.0 * (HYDRO_GAMMA - 1.0))
+        out["therm"][b] = _kick_integral(cosmo, lo, hi, 2.0)
+    return out
+
+
 def cosmological_params(cosmo: Cosmology, ti_current: int, dim=(1.0, 1.0, 1.0),
                         periodic=True, **kw) -> abi.HydroParams:
     """swh_hydro_params of a cosmological step: a, H, a^-2 and the gamma = 5/3

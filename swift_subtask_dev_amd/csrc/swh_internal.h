@@ -187,7 +187,17 @@ struct swh_space {
   swh::DevBuf vfull_s, agrav_s, hasg_s;
   bool xsorted_valid = false;
   bool xparts_valid = false;
-  double vfull_max = 0.;  // max |v_full| of the uploaded xparts (drift displacement bound)
+  double vfull_max = 0.;  // max |v_full| of the xparts (drift displacement bound)
+  // device kicks / timestep (swh_kick.hip). u_full rides in the w lane of
+  // vfull_c / vfull_s. While xsorted_valid the sorted copies are the
+  // authoritative ones: the kicks write them, and a rebuild scatters them back
+  // to caller order before the sort order changes (space_xparts_to_caller).
+  bool has_ufull = false;     // the uploaded xparts carried u_full
+  swh::DevBuf step_rec;       // u64[8]: the record the step kernel reduces into
+  swh::HostBuf step_host;     // pinned: u64[0..8) record read back, [8..16) its initial values
+  hipEvent_t step_event = nullptr;  // behind the last record copy
+  bool step_pending = false;  // a record copy is queued and not yet read (vfull_max)
+  bool step_has_ts = false;   // the record holds a timestep's fields
   // grid
   swh::DevBuf cell_start;  // int32[ncell+1], indexed by Morton rank
   swh::DevBuf cell_rank;   // int32[ncell]: linear cell -> Morton rank

@@ -63,6 +63,16 @@ inline GridDev grid_dev(const swh_space* s) {
 }
 
 SoA soa_of(swh_space* s);
+// The xparts in sorted order (v_full + u_full, a_grav, the gpart flag):
+// gathered from the caller-order copies unless they are current. From then on
+// the sorted copies are the authoritative ones (the kicks write them).
+swh_status space_ensure_xsorted(swh_space* s);
+// Write the sorted v_full / u_full back to the caller-order copy (before the
+// sort order changes, or for a download).
+swh_status space_xparts_to_caller(swh_space* s);
+// swh_kick.hip: wait for the latest step record, if one is queued, and take
+// its max |v_full| as the drift's displacement bound.
+swh_status space_fetch_step_record(swh_space* s);
 // Recompute max h over the set into the device slot counters[2] (float bits).
 swh_status space_hmax_to_device(swh_space* s);
 

@@ -121,6 +121,7 @@ __global__ void pack_kernel(Layout L, char* __restrict__ aos, int64_t n, SoA a, 
     put_f(r, L.soundspeed, th.w);
     put_f(r, L.v_sig, a.grad[s].x);
   }
+  if (fields & SWH_FIELDS_TIMEBIN) *reinterpret_cast<int8_t*>(r + L.time_bin) = a.tb[s];
 }
 
 // Per-block partial bounding box + max h over non-inhibited particles.
@@ -428,15 +429,16 @@ __global__ void pcell_kernel(const uint32_t* __restrict__ keys, const int* __res
   if (s < n) pcell[s] = keys[s] < (uint32_t)ncell ? lin[keys[s]] : -1;
 }
 
-// xparts (caller order) -> v_full, a_grav (caller order; the drift reads them
-// through perm)
+// xparts (caller order) -> v_full (u_full in its w lane), a_grav (caller
+// order; xsort_kernel gathers them into sorted order)
 __global__ void xunpack_kernel(swh_xpart_layout XL, const char* __restrict__ aos, int64_t n,
                                float4* __restrict__ vfull, float4* __restrict__ agrav) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const char* r = aos + i * XL.stride;
   const float* v = reinterpret_cast<const float*>(r + XL.off_v_full);
-  vfull[i] = make_float4(v[0], v[1], v[2], 0.f);
+  const float u_full = XL.off_u_full >= 0 ? *reinterpret_cast<const float*>(r + XL.off_u_full) : 0.f;
+  vfull[i] = make_float4(v[0], v[1], v[2], u_full);
   if (XL.off_a_grav >= 0) {
     const float* g = reinterpret_cast<const float*>(r + XL.off_a_grav);
     agrav[i] = make_float4(g[0], g[1], g[2], 0.f);
@@ -483,6 +485,13 @@ __global__ void xsort_kernel(const int* __restrict__ perm, const float4* __restr
   vfull_s[s] = vfull[c];
   agrav_s[s] = agrav[c];
   hasg_s[s] = hasg[c];
+}
+
+// sorted v_full / u_full -> caller order (the kicks write the sorted copy)
+__global__ void xunsort_kernel(const int* __restrict__ perm, const float4* __restrict__ vfull_s,
+                               int64_t n, float4* __restrict__ vfull) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < n) vfull[perm[s]] = vfull_s[s];
 }
 
 __global__ __launch_bounds__(256) void drift_kernel(SoA a, const float4* __restrict__ vfull,
@@ -676,6 +685,29 @@ swh_status space_hmax_to_device(swh_space* s) {
   return SWH_OK;
 }
 
+swh_status space_ensure_xsorted(swh_space* s) {
+  if (s->xsorted_valid) return SWH_OK;
+  SWH_TRY(s->vfull_s.reserve((size_t)s->n * sizeof(float4)));
+  SWH_TRY(s->agrav_s.reserve((size_t)s->n * sizeof(float4)));
+  SWH_TRY(s->hasg_s.reserve((size_t)s->n));
+  hipLaunchKernelGGL(xsort_kernel, dim3((int)((s->n + 255) / 256)), dim3(256), 0, s->stream,
+                     s->perm.as<const int>(), s->vfull_c.as<const float4>(),
+                     s->agrav_c.as<const float4>(), s->hasg_c.as<const int8_t>(), s->n,
+                     s->vfull_s.as<float4>(), s->agrav_s.as<float4>(), s->hasg_s.as<int8_t>());
+  SWH_HIP(hipGetLastError());
+  s->xsorted_valid = true;
+  return SWH_OK;
+}
+
+swh_status space_xparts_to_caller(swh_space* s) {
+  if (!s->xparts_valid || !s->xsorted_valid || s->n == 0) return SWH_OK;
+  hipLaunchKernelGGL(xunsort_kernel, dim3((int)((s->n + 255) / 256)), dim3(256), 0, s->stream,
+                     s->perm.as<const int>(), s->vfull_s.as<const float4>(), s->n,
+                     s->vfull_c.as<float4>());
+  SWH_HIP(hipGetLastError());
+  return SWH_OK;
+}
+
 }  // namespace swh
 
 extern "C" {
@@ -708,8 +740,11 @@ swh_status swh_space_destroy(swh_space* s) {
                     &s->ghost_right, &s->ghost_list, &s->ghost_list2, &s->ghost_search, &s->ghost_seg, &s->grown_q,
                     &s->grown_mark, &s->grown_search,
                     &s->nbr, &s->nbr_cnt, &s->nbr_base, &s->nbr_reach, &s->nbr_ovf, &s->posf, &s->gplan, &s->ctr_stripes,
-                    &s->iperm, &s->vfull_s, &s->agrav_s, &s->hasg_s, &s->list_xd0};
+                    &s->iperm, &s->vfull_s, &s->agrav_s, &s->hasg_s, &s->list_xd0,
+                    &s->step_rec};
   for (DevBuf* b : bufs) b->release();
+  s->step_host.release();
+  if (s->step_event) (void)hipEventDestroy(s->step_event);
   s->hstage.release();
   s->ghost_host.release();
   if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
@@ -777,7 +812,8 @@ swh_status swh_space_upload_xparts(swh_space* s, const void* xparts, int64_t cou
                                    const swh_xpart_layout* XL, int on_device) {
   if (!s || !XL || (count > 0 && !xparts) || count != s->n || XL->stride <= 0 ||
       XL->off_v_full < 0 || XL->off_v_full + 12 > XL->stride ||
-      (XL->off_a_grav >= 0 && XL->off_a_grav + 12 > XL->stride)) {
+      (XL->off_a_grav >= 0 && XL->off_a_grav + 12 > XL->stride) ||
+      (XL->off_u_full >= 0 && XL->off_u_full + 4 > XL->stride)) {
     set_error("xparts must match the uploaded parts (count %lld) with v_full in the record",
               (long long)s->n);
     return SWH_ERR_ARG;
@@ -795,7 +831,8 @@ swh_status swh_space_upload_xparts(swh_space* s, const void* xparts, int64_t cou
                      s->agrav_c.as<float4>());
   SWH_HIP(hipGetLastError());
   // the fastest particle bounds every displacement of the following drifts
-  // (v_full is fixed until the next upload), so the drift needs no read-back
+  // (v_full changes only in the device kicks, which measure it again), so the
+  // drift needs no read-back of its own
   if (!s->counters.ptr) {
     SWH_TRY(s->counters.reserve(128));
     SWH_HIP(hipMemsetAsync(s->counters.ptr, 0, 128, s->stream));
@@ -813,6 +850,9 @@ swh_status swh_space_upload_xparts(swh_space* s, const void* xparts, int64_t cou
   s->vfull_max = (double)vmax;
   s->xparts_valid = true;
   s->xsorted_valid = false;
+  s->has_ufull = XL->off_u_full >= 0;
+  s->step_pending = false;  // records of kicks before this upload are void
+  s->step_has_ts = false;
   return SWH_OK;
 }
 
@@ -833,16 +873,11 @@ swh_status swh_space_drift(swh_space* s, const swh_drift_params* D, const swh_hy
   unsigned int* ctr = s->counters.as<unsigned int>();
   unsigned int* dx_bits = ctr + 19;  // counter slot 19: drift displacement
   SWH_HIP(hipMemsetAsync(dx_bits, 0, sizeof(unsigned int), st));
-  if (!s->xsorted_valid) {
-    SWH_TRY(s->vfull_s.reserve((size_t)s->n * sizeof(float4)));
-    SWH_TRY(s->agrav_s.reserve((size_t)s->n * sizeof(float4)));
-    SWH_TRY(s->hasg_s.reserve((size_t)s->n));
-    hipLaunchKernelGGL(xsort_kernel, dim3((int)((s->n + 255) / 256)), dim3(256), 0, st,
-                       s->perm.as<const int>(), s->vfull_c.as<const float4>(),
-                       s->agrav_c.as<const float4>(), s->hasg_c.as<const int8_t>(), s->n,
-                       s->vfull_s.as<float4>(), s->agrav_s.as<float4>(), s->hasg_s.as<int8_t>());
-    s->xsorted_valid = true;
-  }
+  SWH_TRY(space_ensure_xsorted(s));
+  // a device kick changed v_full: its record holds the new max |v_full|. If
+  // the caller has not fetched it (swh_space_step_result) this waits for it --
+  // the one host synchronisation of a device-resident step
+  SWH_TRY(space_fetch_step_record(s));
   hipLaunchKernelGGL(drift_kernel, dim3((int)std::min<int64_t>((s->n + 255) / 256, 4 * kReduceBlocks)), dim3(256), 0, st, soa_of(s),
                      s->vfull_s.as<const float4>(), s->agrav_s.as<const float4>(),
                      s->hasg_s.as<const int8_t>(), s->xdiff.as<float4>(), s->n, dp, dx_bits,
@@ -850,9 +885,9 @@ swh_status swh_space_drift(swh_space* s, const swh_drift_params* D, const swh_hy
   SWH_HIP(hipGetLastError());
   // every loop widens its reach by the displacement since the rebuild: bounded
   // by |v_full|_max * dt per drift (the drift kernel keeps the exact per-particle
-  // offsets for the next rebuild); no device read-back, the drift stays
-  // asynchronous. The periodic reach check (h grown past half the box) runs
-  // at the next ghost and rebuild.
+  // offsets for the next rebuild); no device read-back of its own, the drift
+  // stays asynchronous behind the kick's record. The periodic reach check (h
+  // grown past half the box) runs at the next ghost and rebuild.
   s->grid.dx += s->vfull_max * std::fabs(D->dt_drift) * (1. + 1e-6) + 1e-12;
   // positions moved: kept lists (list_keep) are checked against their skin on
   // the device before the next loop uses them; otherwise they are rebuilt
@@ -901,6 +936,8 @@ swh_status swh_space_upload_parts(swh_space* s, const void* parts, int64_t count
   SWH_TRY(s->hasg_c.reserve((size_t)count));
   s->xparts_valid = false;
   s->xsorted_valid = false;
+  s->step_pending = false;
+  s->step_has_ts = false;
   s->grid.dx = 0.;
   hipLaunchKernelGGL(unpack_kernel, dim3(grid), dim3(block), 0, s->stream, L,
                      s->aos.as<const char>(), count, soa_of(s), s->hasg_c.as<int8_t>());
@@ -983,7 +1020,10 @@ swh_status swh_space_rebuild(swh_space* s, const swh_hydro_params* P, double min
   SWH_HIP(hipSetDevice(s->ctx->device));
   hipStream_t st = s->stream;
   s->list_valid = false;
-  s->xsorted_valid = false;  // the sort order changes
+  // the sort order changes: kicked v_full / u_full go back to caller order
+  // first and are gathered again by the next drift or kick
+  SWH_TRY(space_xparts_to_caller(s));
+  s->xsorted_valid = false;
   // 1. bounding box + max h
   const int nb = 512;
   SWH_TRY(s->scan_tmp.reserve(nb * 8 * sizeof(double)));

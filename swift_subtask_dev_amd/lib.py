@@ -51,6 +51,8 @@ HIP_SYMBOLS = [
     "swh_gspace_set_multipoles", "swh_gspace_grav_down",
     "swh_gspace_download", "swh_gspace_sync", "swh_gspace_query", "swh_gspace_pm_mesh",
     "swh_grav_m2l_pairs", "swh_grav_m2l_accept",
+    "swh_space_kick1", "swh_space_kick2", "swh_space_timestep", "swh_space_end_step",
+    "swh_space_step_result", "swh_space_download_xparts", "swh_space_upload_a_grav",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -141,6 +143,14 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
         "swh_space_unpack_halo": (C.c_int, [vp, vp, i32, vp, C.c_int]),
         "swh_space_upload_xparts": (C.c_int, [vp, vp, i64, P(abi.XPartLayout), C.c_int]),
         "swh_space_drift": (C.c_int, [vp, P(abi.DriftParams), P(abi.HydroParams)]),
+        "swh_space_kick1": (C.c_int, [vp, P(abi.KickParams), P(abi.HydroParams)]),
+        "swh_space_kick2": (C.c_int, [vp, P(abi.KickParams), P(abi.HydroParams)]),
+        "swh_space_timestep": (C.c_int, [vp, P(abi.TimestepParams), P(abi.HydroParams)]),
+        "swh_space_end_step": (C.c_int, [vp, P(abi.KickParams), P(abi.TimestepParams),
+                                         P(abi.KickParams), P(abi.HydroParams)]),
+        "swh_space_step_result": (C.c_int, [vp, P(abi.StepResult)]),
+        "swh_space_download_xparts": (C.c_int, [vp, vp, P(abi.XPartLayout), C.c_int]),
+        "swh_space_upload_a_grav": (C.c_int, [vp, vp, C.c_int]),
         "swh_space_set_tuning": (C.c_int, [vp, P(abi.Tuning)]),
         "swh_space_get_info": (C.c_int, [vp, P(abi.SpaceInfo)]),
         "swh_gspace_create": (C.c_int, [vp, P(vp)]),
@@ -412,10 +422,53 @@ class HydroSpace:
 
     def upload_xparts(self, xparts: np.ndarray):
         """struct xpart array (abi.XPART_DTYPE), same order/count as the parts."""
-        XL = abi.XPartLayout(abi.XPART_DTYPE.itemsize, abi.XPART_DTYPE.fields["v_full"][1],
-                             abi.XPART_DTYPE.fields["a_grav"][1])
+        XL = abi.xpart_layout()
         _check(self._lib.swh_space_upload_xparts(self.handle, _ptr(xparts), len(xparts),
                                                  C.byref(XL), 0), "upload_xparts", self._lib)
+
+    def download_xparts(self, xparts: np.ndarray):
+        """v_full and u_full as the device kicks left them, caller order."""
+        XL = abi.xpart_layout()
+        _check(self._lib.swh_space_download_xparts(self.handle, _ptr(xparts), C.byref(XL), 0),
+               "download_xparts", self._lib)
+
+    def upload_a_grav(self, a_grav: np.ndarray):
+        """A new xp->a_grav (n x 3 float32, caller order); v_full stays."""
+        a = np.ascontiguousarray(a_grav, dtype=np.float32)
+        if a.shape != (self._lib.swh_space_count(self.handle), 3):
+            raise ValueError(f"a_grav must be n x 3, got {a.shape}")
+        _check(self._lib.swh_space_upload_a_grav(self.handle, _ptr(a), 0), "upload_a_grav",
+               self._lib)
+
+    def kick1(self, K: abi.KickParams, P: abi.HydroParams):
+        """runner_do_kick1 for the parts: first half of the (new) step."""
+        _check(self._lib.swh_space_kick1(self.handle, C.byref(K), C.byref(P)), "kick1", self._lib)
+
+    def kick2(self, K: abi.KickParams, P: abi.HydroParams):
+        """runner_do_kick2 for the parts: second half-kick, predicted values reset."""
+        _check(self._lib.swh_space_kick2(self.handle, C.byref(K), C.byref(P)), "kick2", self._lib)
+
+    def timestep(self, T: abi.TimestepParams, P: abi.HydroParams):
+        """runner_do_timestep for the parts: new time bins and the step record."""
+        _check(self._lib.swh_space_timestep(self.handle, C.byref(T), C.byref(P)), "timestep",
+               self._lib)
+
+    def end_step(self, K2: abi.KickParams, T: abi.TimestepParams, K1: abi.KickParams,
+                 P: abi.HydroParams):
+        """kick2, timestep and kick1 in one launch."""
+        _check(self._lib.swh_space_end_step(self.handle, C.byref(K2), C.byref(T), C.byref(K1),
+                                            C.byref(P)), "end_step", self._lib)
+
+    def step_result(self, check: bool = True) -> dict:
+        """Waits for the last timestep / end_step and returns its record. A
+        particle below dt_min raises (SWIFT error()s there) unless check=False."""
+        r = abi.StepResult()
+        st = self._lib.swh_space_step_result(self.handle, C.byref(r))
+        if st != 0 and (check or r.n_below_dt_min == 0 or st != 1):
+            _check(st, "step_result", self._lib)
+        return {"ti_end_min": r.ti_end_min, "ti_end_max": r.ti_end_max,
+                "ti_beg_max": r.ti_beg_max, "n_updated": r.n_updated,
+                "n_below_dt_min": r.n_below_dt_min, "vfull_max": r.vfull_max}
 
     def drift(self, D: abi.DriftParams, P: abi.HydroParams):
         _check(self._lib.swh_space_drift(self.handle, C.byref(D), C.byref(P)), "drift", self._lib)
