@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define SWH_ABI_VERSION 12
+#define SWH_ABI_VERSION 13
 
 #if defined(__GNUC__)
 #define SWH_API __attribute__((visibility("default")))
@@ -592,6 +592,39 @@ typedef struct swh_grav_tree_stats {
                              runner_dopair/doself_grav_pp_truncated) -- ABI v10 */
 } swh_grav_tree_stats;
 SWH_API swh_status swh_gspace_set_tree(swh_gspace *g, const swh_gcell *cells, int32_t ncells);
+/* The cell tree built on the device (ABI v13), the stand-in for space_split
+ * (src/space_split.c): a cdim^3 grid of top-level cells over the cubic box,
+ * each split into octants while it holds more than split_size gparts and is
+ * shallower than max_depth; empty octants get no cell. The uploaded records
+ * are sorted into tree order on the device (by top-level cell, then by the
+ * 63-bit Morton key of the position inside it, equal keys in their previous
+ * order), so swh_gspace_download returns them in that order, and the table
+ * is installed exactly as swh_gspace_set_tree would: cells in depth-first
+ * preorder, the roots in ascending top-level cell order, ownership and given
+ * multipoles cleared. Positions outside [0, box) are wrapped. No gpart
+ * leaves the device; the host reads one count per level and the table.
+ * SWH_ERR_ARG for parameters out of range or a non-finite position (the
+ * gspace is unchanged then), SWH_ERR_STATE before any upload. */
+typedef struct swh_tree_params {
+  int32_t cdim;        /* top-level cells per axis (>= 1, cdim^3 <= 2^21) */
+  int32_t split_size;  /* a cell with more gparts than this is split (>= 1) */
+  int32_t max_depth;   /* no cell deeper than this is split (0..20) */
+  int32_t reserved;
+  double box;          /* cubic box side (> 0) */
+} swh_tree_params;
+SWH_API swh_status swh_gspace_build_tree(swh_gspace *g, const swh_tree_params *T,
+                                         int32_t *ncells, int32_t *ntops);
+/* The table of the current tree (built or set) and its top-level cells
+ * (the cells without a parent, ascending); either pointer may be NULL. */
+SWH_API swh_status swh_gspace_get_tree(swh_gspace *g, swh_gcell *cells, int32_t ncells,
+                                       int32_t *tops, int32_t ntops);
+/* order[k] = index, in the last swh_gspace_upload, of the gpart now at k
+ * (successive builds compose; the identity before the first). */
+SWH_API swh_status swh_gspace_tree_order(swh_gspace *g, int32_t *order);
+/* Device time of the last swh_gspace_build_tree (ms, HIP events on the
+ * gspace's stream): ms[0..5) = keys, sorts, gather, levels (with the host's
+ * reads of the level counts), finalisation (with the shared bookkeeping). */
+SWH_API swh_status swh_gspace_build_tree_times(swh_gspace *g, float *ms);
 /* Ownership for a step sharded over ranks (i-cells owned per GPU,
  * every gpart and multipole replicated read-only): owned[c] != 0 for the
  * cells whose gparts this rank computes. swh_grav_tree then runs only the

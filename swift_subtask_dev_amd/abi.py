@@ -97,7 +97,7 @@ XPART_DTYPE = np.dtype(
 )
 
 # include/swifthip.h SWH_ABI_VERSION: the ctypes layouts below are written for it
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 NUM_TIME_BINS = 56  # src/timeline.h:36
 TIME_BIN_INHIBITED = NUM_TIME_BINS + 2
@@ -298,6 +298,13 @@ class GCell(C.Structure):
 GCELL_DTYPE = np.dtype({"names": ["start", "count", "split", "progeny", "loc", "width"],
                         "formats": ["<i4", "<i4", "<i4", ("<i4", 8), ("<f8", 3), ("<f8", 3)],
                         "offsets": [0, 4, 8, 12, 48, 72], "itemsize": 96})
+
+
+class TreeParams(C.Structure):
+    """swh_tree_params (swh_gspace_build_tree)."""
+
+    _fields_ = [("cdim", C.c_int32), ("split_size", C.c_int32), ("max_depth", C.c_int32),
+                ("reserved", C.c_int32), ("box", C.c_double)]
 
 
 class GravTreeStats(C.Structure):

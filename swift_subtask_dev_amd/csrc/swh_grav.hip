@@ -1366,6 +1366,7 @@ swh_status swh_gspace_destroy(swh_gspace* g) {
                     &g->m2p_bits};
   for (DevBuf* b : bufs) b->release();
   mesh_release(g);
+  gtree_release(g);
   (void)hipStreamDestroy(g->stream);
   delete g;
   return SWH_OK;
@@ -1382,6 +1383,8 @@ swh_status swh_gspace_upload(swh_gspace* g, const void* gparts, int64_t count,
   SWH_HIP(hipSetDevice(g->ctx->device));
   g->layout = L;
   g->n = count;
+  g->uploaded = true;
+  g->order_valid = false;  // swh_gspace_tree_order: the records are in upload order
   if (count == 0) return SWH_OK;
   SWH_TRY(g->aos.reserve((size_t)count * L.stride));
   SWH_TRY(g->pos.reserve((size_t)count * sizeof(double4)));
@@ -2346,12 +2349,12 @@ static swh_status device_walk(swh_gspace* g, const swh_grav_params* G, const int
   return SWH_OK;
 }
 
-}  // namespace swh
-
-extern "C" {
-
-swh_status swh_gspace_set_tree(swh_gspace* g, const swh_gcell* cells, int32_t ncells) {
-  if (!g || ncells < 0 || (ncells > 0 && !cells)) return SWH_ERR_ARG;
+// The bookkeeping of a cell table: checks, parents, the depth-grouped L2L and
+// M2M lists, the leaf ids and leaf_of. swh_gspace_set_tree takes the caller's
+// table (leaf_of filled on the host and uploaded, the table copied to tree_d);
+// swh_gspace_build_tree's is already in tree_d and a kernel fills leaf_of.
+swh_status gtree_install(swh_gspace* g, const swh_gcell* cells, int32_t ncells,
+                         bool device_built) {
   g->mpoles_given = false;
   std::vector<int> parent(ncells, -1);
   for (int c = 0; c < ncells; c++) {
@@ -2432,11 +2435,13 @@ swh_status swh_gspace_set_tree(swh_gspace* g, const swh_gcell* cells, int32_t nc
   }
   std::vector<int> leaves;
   std::vector<swh_leaf> ranges(ncells);
-  std::vector<int> leaf_of((size_t)g->n, -1);  // gpart -> its leaf cell (L2P)
+  // gpart -> its leaf cell (L2P)
+  std::vector<int> leaf_of(device_built ? (size_t)0 : (size_t)g->n, -1);
   for (int c = 0; c < ncells; c++) {
     if (!cells[c].split) {
       leaves.push_back(c);
-      for (int k = cells[c].start; k < cells[c].start + cells[c].count; k++) leaf_of[k] = c;
+      if (!device_built)
+        for (int k = cells[c].start; k < cells[c].start + cells[c].count; k++) leaf_of[k] = c;
     }
     ranges[c] = swh_leaf{cells[c].start, cells[c].count};
   }
@@ -2444,14 +2449,17 @@ swh_status swh_gspace_set_tree(swh_gspace* g, const swh_gcell* cells, int32_t nc
   std::vector<int32_t> off(ncells + 1, 0);
   SWH_TRY(swh_gspace_set_leaves(g, ranges.data(), ncells, off.data(), nullptr, 0));
   SWH_HIP(hipSetDevice(g->ctx->device));
-  g->tree.assign(cells, cells + ncells);
+  if (cells != g->tree.data()) g->tree.assign(cells, cells + ncells);
   g->tree_parent = parent;
+  g->tree_tops.clear();
+  for (int c = 0; c < ncells; c++)
+    if (parent[c] < 0) g->tree_tops.push_back(c);
   g->owned.clear();
   SWH_TRY(g->cell_act.reserve((size_t)std::max(1, ncells)));
   SWH_TRY(g->ftens.reserve((size_t)std::max(1, ncells) * SWH_MPOLE_TERMS * sizeof(double)));
   SWH_TRY(g->l2l_list.reserve(std::max<size_t>(1, l2l.size()) * sizeof(int2)));
   SWH_TRY(g->leaf_ids.reserve(std::max<size_t>(1, leaves.size()) * sizeof(int)));
-  SWH_TRY(g->leaf_of.reserve(std::max<size_t>(1, leaf_of.size()) * sizeof(int)));
+  SWH_TRY(g->leaf_of.reserve(std::max<size_t>(1, (size_t)g->n) * sizeof(int)));
   SWH_TRY(g->m2m_list.reserve(std::max<size_t>(1, m2m.size()) * sizeof(int)));
   if (!m2m.empty())
     SWH_HIP(hipMemcpyAsync(g->m2m_list.ptr, m2m.data(), m2m.size() * sizeof(int),
@@ -2472,6 +2480,7 @@ swh_status swh_gspace_set_tree(swh_gspace* g, const swh_gcell* cells, int32_t nc
   int32_t ml = 0;
   for (int c : leaves) ml = std::max(ml, cells[c].count);
   g->tree_max_leaf = ml;
+  if (device_built) return gtree_fill_leaf_of(g, ncells);
   SWH_TRY(g->tree_d.reserve((size_t)std::max(1, ncells) * sizeof(swh_gcell)));
   if (ncells > 0) {
     SWH_HIP(hipMemcpyAsync(g->tree_d.ptr, cells, (size_t)ncells * sizeof(swh_gcell),
@@ -2479,6 +2488,15 @@ swh_status swh_gspace_set_tree(swh_gspace* g, const swh_gcell* cells, int32_t nc
     SWH_HIP(hipStreamSynchronize(g->stream));
   }
   return SWH_OK;
+}
+
+}  // namespace swh
+
+extern "C" {
+
+swh_status swh_gspace_set_tree(swh_gspace* g, const swh_gcell* cells, int32_t ncells) {
+  if (!g || ncells < 0 || (ncells > 0 && !cells)) return SWH_ERR_ARG;
+  return gtree_install(g, cells, ncells, false);
 }
 
 swh_status swh_gspace_set_owned_cells(swh_gspace* g, const uint8_t* owned, int32_t ncells) {

@@ -289,8 +289,33 @@ struct swh_gspace {
   bool mesh_plans_valid = false;
   void* mesh_fwd = nullptr;
   void* mesh_inv = nullptr;
+  // device tree build (swh_gspace_build_tree, swh_gtree.hip). Scratch is kept
+  // across builds: a rebuild of a set of the same size allocates nothing.
+  bool uploaded = false;      // swh_gspace_upload was called
+  bool order_valid = false;   // gt_order holds the permutation since the last upload
+  std::vector<int32_t> tree_tops;  // the roots of the current tree, ascending
+  swh::DevBuf gt_mort, gt_mort2;   // u64: Morton key per gpart, its sorted copy
+  swh::DevBuf gt_tkey, gt_tkey2;   // u32: top-level cell per gpart
+  swh::DevBuf gt_idx, gt_idx2;     // i32: sort payloads (source index)
+  swh::DevBuf gt_aos2;             // the gathered records (swapped with aos)
+  swh::DevBuf gt_order, gt_order2; // i32: index in the last upload of the gpart at k
+  swh::DevBuf gt_tmp;              // hipcub scratch
+  swh::DevBuf gt_tstart;           // i32[cdim^3 + 1]: first gpart of each top-level cell
+  swh::DevBuf gt_cnt, gt_scan;     // i32: per-cell counts of a level and their scan
+  swh::DevBuf gt_bcell;            // the cells level by level, as the split emits them
+  swh::DevBuf gt_pk, gt_pk2, gt_pv, gt_pv2, gt_rank;  // preorder ranking
+  swh::DevBuf gt_flag;             // i32: a non-finite position was seen
+  swh::HostBuf gt_host;            // pinned: the level counts and the flag read back
+  hipEvent_t gt_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool gt_timed = false;           // gt_ev bracket a finished build
 };
 
 namespace swh {
 void mesh_release(swh_gspace* g);  // swh_mesh.hip: mesh buffers and hipFFT plans
+void gtree_release(swh_gspace* g);  // swh_gtree.hip: the tree build's scratch and events
+// swh_grav.hip: the bookkeeping of a cell table, shared by swh_gspace_set_tree
+// and swh_gspace_build_tree. device_built: the table is already in tree_d and
+// leaf_of is filled on the device (gtree_fill_leaf_of), nothing O(N) on the host.
+swh_status gtree_install(swh_gspace* g, const swh_gcell* cells, int32_t ncells, bool device_built);
+swh_status gtree_fill_leaf_of(swh_gspace* g, int32_t ncells);  // swh_gtree.hip
 }

@@ -49,6 +49,8 @@ HIP_SYMBOLS = [
     "swh_gspace_set_tree", "swh_gspace_set_owned_cells", "swh_grav_tree",
     "swh_grav_tree_tasks", "swh_gspace_field_tensors", "swh_gspace_multipoles",
     "swh_gspace_set_multipoles", "swh_gspace_grav_down",
+    "swh_gspace_build_tree", "swh_gspace_get_tree", "swh_gspace_tree_order",
+    "swh_gspace_build_tree_times",
     "swh_gspace_download", "swh_gspace_sync", "swh_gspace_query", "swh_gspace_pm_mesh",
     "swh_grav_m2l_pairs", "swh_grav_m2l_accept",
     "swh_space_kick1", "swh_space_kick2", "swh_space_timestep", "swh_space_end_step",
@@ -160,6 +162,10 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
         "swh_grav_pp_batch": (C.c_int, [vp, P(abi.GravParams), P(i64), P(i64)]),
         "swh_gspace_make_multipoles": (C.c_int, [vp, vp]),
         "swh_gspace_set_tree": (C.c_int, [vp, vp, i32]),
+        "swh_gspace_build_tree": (C.c_int, [vp, P(abi.TreeParams), P(i32), P(i32)]),
+        "swh_gspace_get_tree": (C.c_int, [vp, vp, i32, vp, i32]),
+        "swh_gspace_tree_order": (C.c_int, [vp, vp]),
+        "swh_gspace_build_tree_times": (C.c_int, [vp, P(C.c_float)]),
         "swh_gspace_set_owned_cells": (C.c_int, [vp, P(C.c_uint8), i32]),
         "swh_grav_tree": (C.c_int, [vp, P(abi.GravParams), vp, i32, vp, i32,
                                     P(abi.GravTreeStats)]),
@@ -523,6 +529,7 @@ class GravSpace:
     def upload(self, gparts: np.ndarray):
         _check(self._lib.swh_gspace_upload(self.handle, _ptr(gparts), len(gparts),
                                            C.byref(self.ctx.GL), 0), "gspace_upload", self._lib)
+        self._n = len(gparts)
 
     def set_leaves(self, leaves: np.ndarray, pair_offset: np.ndarray, pairs: np.ndarray):
         leaves = np.ascontiguousarray(leaves, dtype=abi.LEAF_DTYPE)
@@ -557,6 +564,36 @@ class GravSpace:
         assert cells.dtype.itemsize == C.sizeof(abi.GCell)
         self._tree = cells
         _check(self._lib.swh_gspace_set_tree(self.handle, _ptr(cells), len(cells)), "set_tree", self._lib)
+
+    def build_tree(self, cdim: int, split_size: int = 64, box: float = 1.0,
+                   max_depth: int = 12):
+        """The cell tree of ics.gravity_tree, built on the device
+        (swh_gspace_build_tree): the uploaded gparts are sorted into tree
+        order there (download returns them so, tree_order the permutation)
+        and the table is installed as set_tree would. Returns (cells, tops)."""
+        T = abi.TreeParams(cdim, split_size, max_depth, 0, box)
+        nc, nt = C.c_int32(0), C.c_int32(0)
+        _check(self._lib.swh_gspace_build_tree(self.handle, C.byref(T), C.byref(nc), C.byref(nt)),
+               "build_tree", self._lib)
+        cells = np.zeros(nc.value, dtype=abi.GCELL_DTYPE)
+        tops = np.zeros(nt.value, dtype=np.int32)
+        _check(self._lib.swh_gspace_get_tree(self.handle, _ptr(cells), nc.value, _ptr(tops),
+                                             nt.value), "get_tree", self._lib)
+        self._tree = cells
+        return cells, tops
+
+    def build_tree_ms(self) -> dict:
+        """HIP-event times (ms) of the phases of the last build_tree."""
+        ms = (C.c_float * 5)()
+        _check(self._lib.swh_gspace_build_tree_times(self.handle, ms), "build_tree_times",
+               self._lib)
+        return dict(zip(("keys", "sorts", "gather", "levels", "final"), map(float, ms)))
+
+    def tree_order(self) -> np.ndarray:
+        """order[k] = index, in the last upload, of the gpart now at k."""
+        order = np.zeros(getattr(self, "_n", 0), dtype=np.int32)
+        _check(self._lib.swh_gspace_tree_order(self.handle, _ptr(order)), "tree_order", self._lib)
+        return order
 
     def set_owned_cells(self, owned):
         """Per-cell ownership (uint8, whole subtrees; None: every cell) for a
