@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define SWH_ABI_VERSION 13
+#define SWH_ABI_VERSION 14
 
 #if defined(__GNUC__)
 #define SWH_API __attribute__((visibility("default")))
@@ -710,6 +710,135 @@ typedef struct swh_pm_params {
 } swh_pm_params;
 SWH_API swh_status swh_gspace_pm_mesh(swh_gspace *g, const swh_pm_params *M,
                                       double *potential_out);
+
+/* ------------------------------------------------------------------ */
+/* Device-resident N-body step (ABI v14): the gpart stages of          */
+/* engine_step on a gspace, so a gravity run over many steps never     */
+/* downloads its gparts:                                               */
+/*   swh_gspace_drift     drift_gpart (src/drift.h:102-105) and, when  */
+/*                        periodic, the rebuild's box wrap             */
+/*   swh_gspace_init_grav gravity_init_gpart (gravity.h:182-193)       */
+/*   swh_gspace_end_force runner_do_end_grav_force                     */
+/*                        (src/runner_others.c:700-790): the call's    */
+/*                        accumulated results into the records, then   */
+/*                        gravity_end_force (gravity.h:232-271)        */
+/*   swh_gspace_kick2 / _timestep / _kick1 / _end_step                 */
+/*                        the gpart loops of runner_do_kick2,          */
+/*                        runner_do_timestep and runner_do_kick1       */
+/*                        (src/runner_time_integration.c:482-520,      */
+/*                        841-900, 210-250): kick_gpart,               */
+/*                        get_gpart_timestep, one launch when fused    */
+/* All of a gpart's state lives in its record (v_full, a_grav_mesh,    */
+/* potential_mesh, old_a_grav_norm, time_bin, type), so a later        */
+/* swh_gspace_build_tree carries it through its gather. Every gpart    */
+/* that is not inhibited is drifted and takes part in init / end       */
+/* force when active (time_bin <= max_active_bin); only gparts without */
+/* a counterpart -- type dark matter (1), DM background (2), neutrino  */
+/* (6), src/part_type.h:28-34 -- are kicked and time-stepped (kick1    */
+/* tests the new bin: gpart_is_starting). gravity_predict_extra (the   */
+/* softening update) is not applied: epsilon stays as uploaded. The    */
+/* calls only enqueue on the gspace's stream. Each returns             */
+/* SWH_ERR_STATE before swh_gspace_upload or before                    */
+/* swh_gspace_set_step_layout, and is a no-op for an empty set.        */
+/* ------------------------------------------------------------------ */
+/* The gpart fields of the step that swh_gpart_layout does not name. */
+typedef struct swh_gpart_step_layout {
+  int32_t off_v_full;         /* float[3] */
+  int32_t off_a_grav_mesh;    /* float[3] */
+  int32_t off_potential_mesh; /* float    */
+  int32_t off_type;           /* int8 (enum part_type) */
+} swh_gpart_step_layout;
+SWH_API void swh_gpart_step_layout_multisoftening(swh_gpart_step_layout *out);
+/* Kept across uploads. SWH_ERR_ARG for a field outside the uploaded record
+ * or a float field off 4-byte alignment (checked again, with the fields of
+ * swh_gpart_layout the step touches, when a later upload changes the stride:
+ * the step calls then return SWH_ERR_ARG). */
+SWH_API swh_status swh_gspace_set_step_layout(swh_gspace *g, const swh_gpart_step_layout *L);
+
+typedef struct swh_gdrift_params {
+  double dt_drift;  /* non-cosmological: (ti_new - ti_old) * time_base */
+  int32_t periodic; /* wrap x into [0, dim) */
+  int32_t reserved;
+  double dim[3];
+} swh_gdrift_params;
+/* One pass over the records. Afterwards the multipoles are invalid and the
+ * installed tree is stale: its cells cap r_max by the cell corner, so gparts
+ * that left their cell would under-estimate it. swh_grav_tree,
+ * swh_grav_tree_tasks and swh_gspace_grav_down return SWH_ERR_STATE until the
+ * next swh_gspace_build_tree or swh_gspace_set_tree (or a new upload). The
+ * leaf ranges of swh_gspace_set_leaves stay (P2P does not depend on cell
+ * geometry); their multipoles must be made again before the next allow_mpole
+ * batch. */
+SWH_API swh_status swh_gspace_drift(swh_gspace *g, const swh_gdrift_params *D);
+
+/* a_grav = 0, potential = 0 in the records of the active gparts; their
+ * accumulators are cleared too. */
+SWH_API swh_status swh_gspace_init_grav(swh_gspace *g, int32_t max_active_bin);
+
+typedef struct swh_gend_params {
+  float const_G;                 /* physical_constants->const_newton_G */
+  float potential_normalisation; /* 4 pi total_mass r_s^2 / volume (runner_others.c:722-726) */
+  int32_t periodic;
+} swh_gend_params;
+/* For the gparts the last gravity call (swh_grav_pp_batch, swh_grav_tree,
+ * swh_grav_tree_tasks, swh_gspace_grav_down) treated as active: the fp64
+ * accumulators go into the records exactly as swh_gspace_download adds them
+ * (+= (float)acc, accumulator zeroed: a later download adds nothing), then
+ * gravity_end_force: potential += potential_normalisation when periodic,
+ * old_a_grav_norm = |a_grav + a_grav_mesh / const_G| (skipped when the layout
+ * has no old_a_grav_norm), a_grav *= const_G, potential *= const_G,
+ * potential += potential_mesh. */
+SWH_API swh_status swh_gspace_end_force(swh_gspace *g, const swh_gend_params *E);
+
+typedef struct swh_gkick_params {
+  int64_t ti_current;     /* e->ti_current */
+  double time_base;       /* e->time_base  */
+  int32_t max_active_bin; /* e->max_active_bin */
+  int32_t reserved;
+  /* Half-step of every time bin (SWH_NUM_TIME_BINS + 1 entries), nullable, as
+   * swh_kick_params.dt_kick_grav. */
+  const double *dt_kick_grav;
+  /* The mesh kick of this call (runner_time_integration.c:128-138, 400-411):
+   * half a mesh step where one ends (kick2) or starts (kick1), 0 elsewhere. */
+  double dt_kick_mesh_grav;
+} swh_gkick_params;
+
+/* gravity_props / cosmology / engine scalars of get_gpart_timestep
+ * (src/timestep.h:91-131) with gravity_compute_timestep_self. */
+typedef struct swh_gtimestep_params {
+  float eta;                     /* gravity_props->eta */
+  float dt_max_RMS_displacement; /* e->dt_max_RMS_displacement (FLT_MAX: off) */
+  double a;                      /* cosmology->a (1: non-cosmological) */
+  double a_factor_grav_accel;    /* cosmology (1) */
+  double time_step_factor;       /* cosmology (1) */
+  double dt_min, dt_max;         /* e->dt_min, e->dt_max */
+  double time_base_inv;          /* e->time_base_inv */
+  int64_t ti_current;            /* e->ti_current */
+  int32_t max_active_bin;        /* e->max_active_bin */
+  int32_t reserved;
+} swh_gtimestep_params;
+
+SWH_API swh_status swh_gspace_kick1(swh_gspace *g, const swh_gkick_params *K);
+SWH_API swh_status swh_gspace_kick2(swh_gspace *g, const swh_gkick_params *K);
+SWH_API swh_status swh_gspace_timestep(swh_gspace *g, const swh_gtimestep_params *T);
+/* kick2, timestep and kick1 in one launch and one pass; the same bits as the
+ * three calls in a row. */
+SWH_API swh_status swh_gspace_end_step(swh_gspace *g, const swh_gkick_params *K2,
+                                       const swh_gtimestep_params *T,
+                                       const swh_gkick_params *K1);
+/* The record of the last swh_gspace_timestep / swh_gspace_end_step over the
+ * not inhibited gparts of the kicked types, as runner_do_timestep collects it
+ * (:841-900): active gparts end at ti_current + their new step, the others at
+ * the end of the step they are in. vfull_max: max |v_full| of those gparts
+ * after the last kick. The launch copies the record into pinned host memory
+ * behind it; this call waits for that copy, the step's one host wait.
+ * SWH_ERR_STATE when no timestep was queued since the last upload;
+ * SWH_ERR_ARG (the record is still returned) when n_below_dt_min > 0. */
+SWH_API swh_status swh_gspace_step_result(swh_gspace *g, swh_step_result *out);
+/* Device time of the last launch of each stage (ms, HIP events on the
+ * gspace's stream; waits for them): ms[0..4) = drift, init_grav, end_force,
+ * the last kick1 / kick2 / timestep / end_step. -1 for a stage not yet run. */
+SWH_API swh_status swh_gspace_step_times(swh_gspace *g, float *ms);
 
 #ifdef __cplusplus
 }

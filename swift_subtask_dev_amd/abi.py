@@ -97,7 +97,7 @@ XPART_DTYPE = np.dtype(
 )
 
 # include/swifthip.h SWH_ABI_VERSION: the ctypes layouts below are written for it
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 NUM_TIME_BINS = 56  # src/timeline.h:36
 TIME_BIN_INHIBITED = NUM_TIME_BINS + 2
@@ -285,6 +285,79 @@ class PMParams(C.Structure):
 # struct gpart (multi-softening) offsets of the mesh fields (swift_compat.h)
 GPART_OFF_A_GRAV_MESH = 56
 GPART_OFF_POTENTIAL_MESH = 72
+
+
+class GPartStepLayout(C.Structure):
+    """swh_gpart_step_layout: the step's gpart fields beside GPartLayout's."""
+
+    _fields_ = [(n, C.c_int32) for n in ("off_v_full", "off_a_grav_mesh", "off_potential_mesh",
+                                         "off_type")]
+
+
+def gpart_step_layout() -> GPartStepLayout:
+    """The step layout of GPART_DTYPE."""
+    f = GPART_DTYPE.fields
+    return GPartStepLayout(f["v_full"][1], f["a_grav_mesh"][1], f["potential_mesh"][1],
+                           f["type"][1])
+
+
+# enum part_type (src/part_type.h:28-34): the gparts without a counterpart
+GPART_TYPE_GAS, GPART_TYPE_DARK_MATTER, GPART_TYPE_DM_BACKGROUND, GPART_TYPE_NEUTRINO = 0, 1, 2, 6
+GPART_KICKED_TYPES = (GPART_TYPE_DARK_MATTER, GPART_TYPE_DM_BACKGROUND, GPART_TYPE_NEUTRINO)
+
+
+class GDriftParams(C.Structure):
+    """swh_gdrift_params."""
+
+    _fields_ = [("dt_drift", C.c_double), ("periodic", C.c_int32), ("reserved", C.c_int32),
+                ("dim", C.c_double * 3)]
+
+    def __init__(self, dt_drift=0.0, periodic=0, dim=(1.0, 1.0, 1.0)):
+        super().__init__(dt_drift, int(periodic), 0, (C.c_double * 3)(*dim))
+
+
+class GEndParams(C.Structure):
+    """swh_gend_params."""
+
+    _fields_ = [("const_G", C.c_float), ("potential_normalisation", C.c_float),
+                ("periodic", C.c_int32)]
+
+
+class GKickParams(C.Structure):
+    """swh_gkick_params: one half-kick of the gparts."""
+
+    _fields_ = [("ti_current", C.c_int64), ("time_base", C.c_double),
+                ("max_active_bin", C.c_int32), ("reserved", C.c_int32),
+                ("dt_kick_grav", C.POINTER(C.c_double)), ("dt_kick_mesh_grav", C.c_double)]
+
+    def set_table(self, grav=None) -> None:
+        """Per-time-bin half-steps (None: (ti_step / 2) * time_base). The array
+        is kept alive by this object."""
+        self._keep, ptr = _bin_table(grav)
+        self.dt_kick_grav = ptr
+
+
+class GTimestepParams(C.Structure):
+    """swh_gtimestep_params."""
+
+    _fields_ = [("eta", C.c_float), ("dt_max_RMS_displacement", C.c_float), ("a", C.c_double),
+                ("a_factor_grav_accel", C.c_double), ("time_step_factor", C.c_double),
+                ("dt_min", C.c_double), ("dt_max", C.c_double), ("time_base_inv", C.c_double),
+                ("ti_current", C.c_int64), ("max_active_bin", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def default_gtimestep_params(**kw) -> GTimestepParams:
+    """Non-cosmological, eta = 0.025 (SWIFT's examples), no bounds."""
+    T = GTimestepParams()
+    T.eta = 0.025
+    T.dt_max_RMS_displacement = np.finfo(np.float32).max
+    T.a = T.a_factor_grav_accel = T.time_step_factor = 1.0
+    T.dt_min, T.dt_max = 0.0, float(np.finfo(np.float32).max)
+    T.max_active_bin = NUM_TIME_BINS
+    for k, v in kw.items():
+        setattr(T, k, v)
+    return T
 
 
 class GCell(C.Structure):

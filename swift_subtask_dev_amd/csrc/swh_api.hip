@@ -184,6 +184,13 @@ void swh_gpart_layout_multisoftening(swh_gpart_layout* o) {
   o->off_old_a_grav_norm = offsetof(struct gpart, old_a_grav_norm);
 }
 
+void swh_gpart_step_layout_multisoftening(swh_gpart_step_layout* o) {
+  o->off_v_full = offsetof(struct gpart, v_full);
+  o->off_a_grav_mesh = offsetof(struct gpart, a_grav_mesh);
+  o->off_potential_mesh = offsetof(struct gpart, potential_mesh);
+  o->off_type = offsetof(struct gpart, type);
+}
+
 swh_status swh_init(swh_context** out, int device) {
   if (!out) return SWH_ERR_ARG;
   *out = nullptr;

@@ -1367,6 +1367,7 @@ swh_status swh_gspace_destroy(swh_gspace* g) {
   for (DevBuf* b : bufs) b->release();
   mesh_release(g);
   gtree_release(g);
+  gstep_release(g);
   (void)hipStreamDestroy(g->stream);
   delete g;
   return SWH_OK;
@@ -1385,6 +1386,10 @@ swh_status swh_gspace_upload(swh_gspace* g, const void* gparts, int64_t count,
   g->n = count;
   g->uploaded = true;
   g->order_valid = false;  // swh_gspace_tree_order: the records are in upload order
+  g->tree_stale = false;   // a drift's staleness went with the records it moved
+  g->step_checked = false;
+  g->gstep_has_ts = false;
+  g->gstep_pending = false;
   if (count == 0) return SWH_OK;
   SWH_TRY(g->aos.reserve((size_t)count * L.stride));
   SWH_TRY(g->pos.reserve((size_t)count * sizeof(double4)));
@@ -2356,6 +2361,7 @@ static swh_status device_walk(swh_gspace* g, const swh_grav_params* G, const int
 swh_status gtree_install(swh_gspace* g, const swh_gcell* cells, int32_t ncells,
                          bool device_built) {
   g->mpoles_given = false;
+  g->tree_stale = false;
   std::vector<int> parent(ncells, -1);
   for (int c = 0; c < ncells; c++) {
     const swh_gcell& C = cells[c];
@@ -2602,6 +2608,11 @@ swh_status swh_grav_tree_tasks(swh_gspace* g, const swh_grav_params* G,
     set_error("swh_gspace_set_tree must precede swh_grav_tree");
     return ncells == 0 ? SWH_ERR_STATE : SWH_OK;
   }
+  if (g->tree_stale) {
+    set_error("the gparts were drifted since the tree was installed: swh_gspace_build_tree or "
+              "swh_gspace_set_tree must precede swh_grav_tree");
+    return SWH_ERR_STATE;
+  }
   for (int k = 0; k < nself; k++)
     if (self_cells[k] < 0 || self_cells[k] >= ncells) return SWH_ERR_ARG;
   for (int k = 0; k < 2 * npair; k++)
@@ -2823,6 +2834,11 @@ swh_status swh_gspace_grav_down(swh_gspace* g, const swh_grav_params* G, const f
   if (g->n == 0 || ncells == 0) {
     set_error("swh_gspace_set_tree must precede swh_gspace_grav_down");
     return ncells == 0 ? SWH_ERR_STATE : SWH_OK;
+  }
+  if (g->tree_stale) {
+    set_error("the gparts were drifted since the tree was installed: swh_gspace_build_tree or "
+              "swh_gspace_set_tree must precede swh_gspace_grav_down");
+    return SWH_ERR_STATE;
   }
   SWH_HIP(hipSetDevice(g->ctx->device));
   // activity and the accumulators (swh_gspace_download adds them)

@@ -308,11 +308,28 @@ struct swh_gspace {
   swh::HostBuf gt_host;            // pinned: the level counts and the flag read back
   hipEvent_t gt_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool gt_timed = false;           // gt_ev bracket a finished build
+  // device-resident step (swh_gkick.hip): the step's fields beside `layout`,
+  // the record the step kernel reduces into and its pinned copy
+  swh_gpart_step_layout step_layout{-1, -1, -1, -1};
+  bool step_layout_set = false;
+  bool step_checked = false;   // every offset the step kernels use lies inside the stride
+  bool tree_stale = false;     // drifted since the tree was installed (swh_gspace_drift)
+  swh::DevBuf gstep_rec;       // u64 slots, 128 bytes apart
+  swh::HostBuf gstep_host;     // the record read back, then the timestep's dt_min
+  hipEvent_t gstep_event = nullptr;  // behind the last record copy
+  bool gstep_pending = false;  // a record copy is queued and not yet read
+  bool gstep_has_ts = false;   // the record holds a timestep's fields
+  float gstep_vmax = 0.f;      // max |v_full| of the last fetched record
+  // HIP events around the last launch of each stage: drift, init_grav,
+  // end_force, kick / timestep / end_step (swh_gspace_step_times)
+  hipEvent_t gstep_tev[4][2] = {};
+  bool gstep_timed[4] = {false, false, false, false};
 };
 
 namespace swh {
 void mesh_release(swh_gspace* g);  // swh_mesh.hip: mesh buffers and hipFFT plans
 void gtree_release(swh_gspace* g);  // swh_gtree.hip: the tree build's scratch and events
+void gstep_release(swh_gspace* g);  // swh_gkick.hip: the step record's buffers and event
 // swh_grav.hip: the bookkeeping of a cell table, shared by swh_gspace_set_tree
 // and swh_gspace_build_tree. device_built: the table is already in tree_d and
 // leaf_of is filled on the device (gtree_fill_leaf_of), nothing O(N) on the host.

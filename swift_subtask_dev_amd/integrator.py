@@ -26,7 +26,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import abi, cosmo as cosmo_mod
+from . import abi, cosmo as cosmo_mod, ics
 
 MAX_NR_TIMESTEPS = 1 << (abi.NUM_TIME_BINS + 1)
 
@@ -155,4 +155,164 @@ class Integrator:
     @property
     def time(self) -> float:
         """Physical time (non-cosmological) or log(a / a_begin) since the start."""
+        return self.ti_current * self.time_base
+
+
+class NBodyIntegrator:
+    """A multi-step, multi-time-bin driver over one GravSpace: the gparts stay
+    on the device from the first upload on (non-cosmological).
+
+        init_step()      engine_init_particles: every live gpart active in bin
+                         0, the tree build, gravity, the first time steps and
+                         the first half-kick
+        drift_to_next()  ti_current = the record's ti_end_min, drift there,
+                         rebuild the tree (a drifted tree is stale, so every
+                         step rebuilds)
+        gravity()        gravity_init_gpart, the mesh where a mesh step ends,
+                         the tree walk, runner_do_end_grav_force
+        end_step()       kick2 + timestep + kick1 in one launch, then the record
+        step()           the three above
+
+    G: abi.GravParams (its max_active_bin follows the run), T:
+    abi.GTimestepParams (ti_current, max_active_bin and time_base_inv follow
+    the run), mesh: None or dict(N=, r_s=): the periodic long-range force
+    (swh_gspace_pm_mesh) on the schedule of engine.c:3528-3550 without the
+    RMS-displacement term -- the mesh step is the largest step of the time
+    line <= dt_max, every gpart's step is <= dt_max too, so all gparts are
+    active where a mesh step ends; kick2 and kick1 there get half a mesh step
+    (runner_time_integration.c:128-138, 400-411), the others none.
+
+    The step's one host wait is the record read, which delivers ti_end_min."""
+
+    def __init__(self, gspace, G: abi.GravParams, T: abi.GTimestepParams, time_base: float,
+                 cdim: int, split_size: int = 64, max_depth: int = 12, box: float = 1.0,
+                 const_G: float = 1.0, mesh: dict = None):
+        if not time_base or time_base <= 0:
+            raise ValueError("time_base (time per tick) must be positive")
+        self.gs = gspace
+        self.G = G
+        self.T = T
+        self.time_base = float(time_base)
+        self.T.time_base_inv = 1.0 / self.time_base
+        self.cdim, self.split_size, self.max_depth = int(cdim), int(split_size), int(max_depth)
+        self.box = float(box)
+        self.const_G = float(const_G)
+        self.mesh = dict(mesh) if mesh else None
+        self.periodic = bool(G.periodic)
+        self.ti_current = 0
+        self.max_active_bin = abi.NUM_TIME_BINS
+        self.result = None
+        self.tops = None
+        self._pairs = None
+        self.potential_normalisation = 0.0
+        self.mesh_ti_beg = self.mesh_ti_end = -1
+        self.mesh_kicks = 0  # half mesh kicks given so far
+
+    # -- engine scalars at ti_current -------------------------------------
+    def _update_scalars(self):
+        self.G.max_active_bin = self.max_active_bin
+        self.T.max_active_bin = self.max_active_bin
+        self.T.ti_current = self.ti_current
+
+    def _kick_params(self, dt_mesh: float = 0.0) -> abi.GKickParams:
+        K = abi.GKickParams()
+        K.ti_current = self.ti_current
+        K.time_base = self.time_base
+        K.max_active_bin = self.max_active_bin
+        K.dt_kick_mesh_grav = dt_mesh
+        if dt_mesh != 0.0:
+            self.mesh_kicks += 1
+        return K
+
+    def _next_mesh_step(self) -> int:
+        """engine.c:3528-3550 without the RMS term: the length of the mesh
+        step that starts at ti_current."""
+        new_dti = int(self.T.dt_max * self.T.time_base_inv)
+        line = MAX_NR_TIMESTEPS
+        while new_dti < line:
+            line //= 2
+        new_dti = line
+        current = self.mesh_ti_end - self.mesh_ti_beg if self.mesh_ti_end > 0 else MAX_NR_TIMESTEPS
+        if new_dti > current and (MAX_NR_TIMESTEPS - self.ti_current) % new_dti > 0:
+            new_dti = current
+        return new_dti
+
+    def _build(self):
+        _, tops = self.gs.build_tree(self.cdim, self.split_size, self.box, self.max_depth)
+        if self.tops is None or not np.array_equal(tops, self.tops):
+            self.tops = tops
+            self._pairs = ics.top_level_pairs(tops)
+
+    # -- the entry points -----------------------------------------------------
+    def init_step(self, gparts: np.ndarray) -> dict:
+        """Upload the gparts (the only upload of the run), compute their first
+        forces, time steps and half-kick. Live gparts start in time bin 0."""
+        g = abi.copy_parts(gparts)
+        live = g["time_bin"] != abi.TIME_BIN_INHIBITED
+        g["time_bin"] = np.where(live, 0, g["time_bin"]).astype(np.int8)
+        self.ti_current = 0
+        self.max_active_bin = abi.NUM_TIME_BINS
+        self.mesh_ti_beg = self.mesh_ti_end = -1
+        self.mesh_kicks = 0
+        self._update_scalars()
+        if self.mesh and self.periodic:
+            # runner_others.c:722-726
+            total_mass = float(g["mass"][live].astype(np.float64).sum())
+            r_s = float(self.mesh["r_s"])
+            self.potential_normalisation = 4.0 * np.pi * total_mass * r_s * r_s / self.box ** 3
+        self.gs.upload(g)
+        self._build()
+        self.gravity()
+        self.gs.timestep(self.T)
+        dt_mesh = 0.0
+        if self.mesh:
+            self.mesh_ti_beg = 0
+            self.mesh_ti_end = self._next_mesh_step()
+            dt_mesh = (self.mesh_ti_end // 2) * self.time_base
+        self.gs.kick1(self._kick_params(dt_mesh))
+        self.result = self.gs.step_result()
+        return self.result
+
+    def drift_to_next(self) -> float:
+        """Choose the next ti_current, drift there, rebuild the tree."""
+        ti_old = self.ti_current
+        self.ti_current = int(self.result["ti_end_min"])
+        if not ti_old < self.ti_current <= MAX_NR_TIMESTEPS:
+            raise RuntimeError(f"time line exhausted or stalled at {ti_old} -> {self.ti_current}")
+        self.max_active_bin = get_max_active_bin(self.ti_current)
+        self._update_scalars()
+        dt = (self.ti_current - ti_old) * self.time_base
+        self.gs.drift(dt, self.periodic, (self.box,) * 3)
+        self._build()
+        return dt
+
+    def _mesh_step_ends(self) -> bool:
+        return bool(self.mesh) and self.ti_current == self.mesh_ti_end
+
+    def gravity(self):
+        self.gs.init_grav(self.max_active_bin)
+        if self.mesh and (self.ti_current == 0 or self._mesh_step_ends()):
+            self.gs.pm_mesh(int(self.mesh["N"]), self.box, float(self.mesh["r_s"]), self.const_G)
+        self.gs.tree(self.G, self.tops, self._pairs, stats=False)
+        self.gs.end_force(self.const_G, self.potential_normalisation, self.periodic)
+
+    def end_step(self) -> dict:
+        dt2 = dt1 = 0.0
+        if self._mesh_step_ends():
+            dt2 = ((self.mesh_ti_end - self.mesh_ti_beg) // 2) * self.time_base
+            new_dti = self._next_mesh_step()
+            self.mesh_ti_beg = self.ti_current
+            self.mesh_ti_end = self.ti_current + new_dti
+            dt1 = (new_dti // 2) * self.time_base
+        self.gs.end_step(self._kick_params(dt2), self.T, self._kick_params(dt1))
+        self.result = self.gs.step_result()
+        return self.result
+
+    def step(self) -> dict:
+        self.drift_to_next()
+        self.gravity()
+        return self.end_step()
+
+    @property
+    def time(self) -> float:
         return self.ti_current * self.time_base

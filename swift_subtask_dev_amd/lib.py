@@ -55,6 +55,10 @@ HIP_SYMBOLS = [
     "swh_grav_m2l_pairs", "swh_grav_m2l_accept",
     "swh_space_kick1", "swh_space_kick2", "swh_space_timestep", "swh_space_end_step",
     "swh_space_step_result", "swh_space_download_xparts", "swh_space_upload_a_grav",
+    "swh_gpart_step_layout_multisoftening", "swh_gspace_set_step_layout", "swh_gspace_drift",
+    "swh_gspace_init_grav", "swh_gspace_end_force", "swh_gspace_kick1", "swh_gspace_kick2",
+    "swh_gspace_timestep", "swh_gspace_end_step", "swh_gspace_step_result",
+    "swh_gspace_step_times",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -182,6 +186,18 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
         "swh_grav_m2l_pairs": (C.c_int, [vp, P(abi.GravParams), vp, i32, vp, i32, vp]),
         "swh_grav_m2l_accept": (C.c_int, [P(abi.GravParams), P(abi.Multipole),
                                           P(abi.Multipole), dp]),
+        "swh_gpart_step_layout_multisoftening": (None, [P(abi.GPartStepLayout)]),
+        "swh_gspace_set_step_layout": (C.c_int, [vp, P(abi.GPartStepLayout)]),
+        "swh_gspace_drift": (C.c_int, [vp, P(abi.GDriftParams)]),
+        "swh_gspace_init_grav": (C.c_int, [vp, i32]),
+        "swh_gspace_end_force": (C.c_int, [vp, P(abi.GEndParams)]),
+        "swh_gspace_kick1": (C.c_int, [vp, P(abi.GKickParams)]),
+        "swh_gspace_kick2": (C.c_int, [vp, P(abi.GKickParams)]),
+        "swh_gspace_timestep": (C.c_int, [vp, P(abi.GTimestepParams)]),
+        "swh_gspace_end_step": (C.c_int, [vp, P(abi.GKickParams), P(abi.GTimestepParams),
+                                          P(abi.GKickParams)]),
+        "swh_gspace_step_result": (C.c_int, [vp, P(abi.StepResult)]),
+        "swh_gspace_step_times": (C.c_int, [vp, P(C.c_float)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -285,6 +301,8 @@ class Context:
         self.set_precision(precision)
         self.L = part_layout()
         self.GL = gpart_layout()
+        self.GSL = abi.GPartStepLayout()
+        lib.swh_gpart_step_layout_multisoftening(C.byref(self.GSL))
 
     def set_precision(self, precision: str) -> None:
         _check(self._lib.swh_set_precision(self.handle, 0 if precision == "f64" else 1),
@@ -508,12 +526,16 @@ class HydroSpace:
 class GravSpace:
     """Device-resident gpart set for batch P2P (swh_gspace)."""
 
-    def __init__(self, ctx: Context):
+    def __init__(self, ctx: Context, step_layout: bool = True):
+        """step_layout=False leaves the step's layout unset (the step calls
+        then raise until set_step_layout)."""
         self.ctx = ctx
         self._lib = ctx._lib
         h = C.c_void_p()
         _check(self._lib.swh_gspace_create(ctx.handle, C.byref(h)), "swh_gspace_create", self._lib)
         self.handle = h
+        if step_layout:
+            self.set_step_layout(ctx.GSL)
 
     def close(self):
         if self.handle:
@@ -639,6 +661,63 @@ class GravSpace:
     def download(self, gparts: np.ndarray):
         _check(self._lib.swh_gspace_download(self.handle, _ptr(gparts), C.byref(self.ctx.GL), 0),
                "gspace_download", self._lib)
+
+    # ---- device-resident step (swh_gkick.hip) ---------------------------
+    def set_step_layout(self, SL: abi.GPartStepLayout):
+        _check(self._lib.swh_gspace_set_step_layout(self.handle, C.byref(SL)), "set_step_layout",
+               self._lib)
+
+    def drift(self, dt_drift: float, periodic: bool = False, dim=(1.0, 1.0, 1.0)):
+        """drift_gpart on every live gpart (+ the box wrap when periodic). The
+        installed tree is stale afterwards: build_tree or set_tree before tree()."""
+        D = abi.GDriftParams(dt_drift, periodic, dim)
+        _check(self._lib.swh_gspace_drift(self.handle, C.byref(D)), "gspace_drift", self._lib)
+
+    def init_grav(self, max_active_bin: int = abi.NUM_TIME_BINS):
+        """gravity_init_gpart on the active gparts' records."""
+        _check(self._lib.swh_gspace_init_grav(self.handle, max_active_bin), "init_grav", self._lib)
+
+    def end_force(self, const_G: float = 1.0, potential_normalisation: float = 0.0,
+                  periodic: bool = False):
+        """The last gravity call's results into the records, then gravity_end_force."""
+        E = abi.GEndParams(const_G, potential_normalisation, int(periodic))
+        _check(self._lib.swh_gspace_end_force(self.handle, C.byref(E)), "gspace_end_force",
+               self._lib)
+
+    def kick1(self, K: abi.GKickParams):
+        """runner_do_kick1 for the gparts: first half of the (new) step."""
+        _check(self._lib.swh_gspace_kick1(self.handle, C.byref(K)), "gspace_kick1", self._lib)
+
+    def kick2(self, K: abi.GKickParams):
+        """runner_do_kick2 for the gparts: second half of the step that ends."""
+        _check(self._lib.swh_gspace_kick2(self.handle, C.byref(K)), "gspace_kick2", self._lib)
+
+    def timestep(self, T: abi.GTimestepParams):
+        """runner_do_timestep for the gparts: new time bins and the step record."""
+        _check(self._lib.swh_gspace_timestep(self.handle, C.byref(T)), "gspace_timestep",
+               self._lib)
+
+    def end_step(self, K2: abi.GKickParams, T: abi.GTimestepParams, K1: abi.GKickParams):
+        """kick2, timestep and kick1 in one launch."""
+        _check(self._lib.swh_gspace_end_step(self.handle, C.byref(K2), C.byref(T), C.byref(K1)),
+               "gspace_end_step", self._lib)
+
+    def step_result(self, check: bool = True) -> dict:
+        """Waits for the last timestep / end_step and returns its record. A
+        gpart below dt_min raises (SWIFT error()s there) unless check=False."""
+        r = abi.StepResult()
+        st = self._lib.swh_gspace_step_result(self.handle, C.byref(r))
+        if st != 0 and (check or r.n_below_dt_min == 0 or st != 1):
+            _check(st, "gspace_step_result", self._lib)
+        return {"ti_end_min": r.ti_end_min, "ti_end_max": r.ti_end_max,
+                "ti_beg_max": r.ti_beg_max, "n_updated": r.n_updated,
+                "n_below_dt_min": r.n_below_dt_min, "vfull_max": r.vfull_max}
+
+    def step_ms(self) -> dict:
+        """HIP-event times (ms) of the last launch of each stage (-1: not run)."""
+        ms = (C.c_float * 4)()
+        _check(self._lib.swh_gspace_step_times(self.handle, ms), "step_times", self._lib)
+        return dict(zip(("drift", "init_grav", "end_force", "end_step"), map(float, ms)))
 
     def sync(self):
         _check(self._lib.swh_gspace_sync(self.handle), "gspace_sync", self._lib)
