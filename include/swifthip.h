@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define SWH_ABI_VERSION 14
+#define SWH_ABI_VERSION 15
 
 #if defined(__GNUC__)
 #define SWH_API __attribute__((visibility("default")))
@@ -372,9 +372,10 @@ SWH_API swh_status swh_space_drift(swh_space *s, const swh_drift_params *D,
 /* on the device from swh_space_upload_xparts on: the kicks advance    */
 /* them there and a rebuild carries them through the re-sort.          */
 /* a_grav is the total gravitational acceleration the caller uploaded  */
-/* (tree + mesh): there is no separate mesh kick (a_grav_mesh,         */
+/* (tree + mesh): these calls have no separate mesh kick (a_grav_mesh, */
 /* dt_kick_mesh_grav); the caller that integrates the mesh on its own  */
-/* schedule adds it to a_grav for the kicks where it applies.          */
+/* schedule adds it to a_grav for the kicks where it applies. A space  */
+/* linked to a gspace has one: swh_space_kick1_linked and its kin.     */
 /* Entropy and pressure floors NONE, as the drift.                     */
 /* ------------------------------------------------------------------ */
 typedef struct swh_kick_params {
@@ -839,6 +840,92 @@ SWH_API swh_status swh_gspace_step_result(swh_gspace *g, swh_step_result *out);
  * gspace's stream; waits for them): ms[0..4) = drift, init_grav, end_force,
  * the last kick1 / kick2 / timestep / end_step. -1 for a stage not yet run. */
 SWH_API swh_status swh_gspace_step_times(swh_gspace *g, float *ms);
+
+/* ------------------------------------------------------------------ */
+/* Self-gravitating gas (ABI v15): the link between a space's parts    */
+/* and the gas gparts of a gspace, so a coupled hydro + gravity step   */
+/* moves nothing through the host. A gas gpart (type 0) names its part */
+/* as SWIFT does after a sort (src/space.c:1880): id_or_neg_offset,    */
+/* the record's first member, is minus the caller index of the part.   */
+/* The value travels with the record through every tree build and the  */
+/* space keeps caller index -> sorted index through every rebuild, so  */
+/* the link is one indexed access in whatever order either side stores */
+/* its particles. What SWIFT's part loops do for the counterpart:      */
+/*   kick_part (src/kick.h:214-267) reads p->gpart->a_grav and         */
+/*     a_grav_mesh and writes p->gpart->v_full = xp->v_full            */
+/*   get_part_timestep adds a_grav_mesh between the tree and hydro     */
+/*     terms (gravity/MultiSoftening/gravity.h:147-159)                */
+/*   runner_do_timestep writes p->gpart->time_bin = p->time_bin        */
+/*     (src/runner_time_integration.c:747)                             */
+/*   runner_do_kick1 sets xp->a_grav = gp->a_grav + gp->a_grav_mesh    */
+/*     for the drift (:185-190)                                        */
+/* Every call below but swh_space_link_gspace returns SWH_ERR_STATE    */
+/* without a link. Non-cosmological or cosmological alike (the tables  */
+/* of swh_kick_params); one device (a space with foreign particles is  */
+/* refused).                                                           */
+/* ------------------------------------------------------------------ */
+/* Checks the link on the device and waits for the verdict (the one
+ * synchronous call; once per pair of uploads): every gpart of g that is not
+ * inhibited and has type gas must name a part, j = -id_or_neg_offset in
+ * [0, n); no part is named twice; a named part is not inhibited. Refused with
+ * SWH_ERR_ARG (the counts in swh_last_error) on any violation, on different
+ * contexts, a space with foreign particles (swh_space_set_owned), xparts not
+ * uploaded, or no step layout on g; both objects then stay unlinked and
+ * otherwise untouched. On success the gpart flag of the space (what
+ * swh_part_layout.off_gpart delivered) becomes 1 for the named parts and 0 for
+ * the rest, *n_linked (nullable) the number of pairs. The space's a_grav array
+ * keeps its meaning: xp->a_grav, the drift's acceleration. g == NULL unlinks.
+ * Destroying either object unlinks the other; a new swh_space_upload_parts or
+ * swh_gspace_upload drops the link, and so does swh_space_set_owned with
+ * foreign particles. */
+SWH_API swh_status swh_space_link_gspace(swh_space *s, swh_gspace *g, int64_t *n_linked);
+/* After the gspace's swh_gspace_end_force: every linked gas gpart's a_grav and
+ * a_grav_mesh into the space, at its part. One launch on the space's stream
+ * behind the gspace's queued work; no host wait. The values hold until the
+ * next swh_space_rebuild or upload of the space. SWH_ERR_STATE before
+ * swh_space_rebuild. */
+SWH_API swh_status swh_space_pull_gravity(swh_space *s);
+
+#define SWH_PUSH_X 1u        /* x from the part's position */
+#define SWH_PUSH_V_FULL 2u   /* v_full from xp->v_full */
+#define SWH_PUSH_TIME_BIN 4u /* time_bin */
+typedef struct swh_push_params {
+  uint32_t what;    /* SWH_PUSH_* bits */
+  int32_t periodic; /* wrap x into [0, dim) as swh_gspace_drift does */
+  double dim[3];
+} swh_push_params;
+/* For every linked gas gpart, the part's values into the record; all other
+ * bytes of a gas record and every other record stay. One launch on the
+ * gspace's stream behind the space's queued work; no host wait. SWH_PUSH_X
+ * leaves the installed tree stale, as swh_gspace_drift does (the gspace's own
+ * drift still moves the gas gparts first and is overwritten here). */
+SWH_API swh_status swh_space_push_gparts(swh_space *s, const swh_push_params *Q);
+
+/* swh_space_kick1 / _kick2 / _timestep / _end_step for a linked space, the
+ * same kernel: a linked particle is kicked by a_hydro dt_hydro, then the
+ * pulled a_grav dt_grav, then a_grav_mesh dt_kick_mesh_grav (always added,
+ * src/kick.h:236-246), each float += float * double; its time step's gravity
+ * condition takes |(a_grav f_g + a_grav_mesh f_g) + a_hydro f_h|; kick1 sets
+ * xp->a_grav = a_grav + a_grav_mesh (a float add) for the particles it kicks.
+ * The other particles of the space take swh_space_kick1's path. The fused
+ * call and the three calls give the same bits. SWH_ERR_STATE when no
+ * swh_space_pull_gravity happened since the last rebuild or upload: a step's
+ * active gas particles are those whose gparts were active, so what they read
+ * is this step's force. dt_kick_mesh_grav as swh_gkick_params'. */
+SWH_API swh_status swh_space_kick1_linked(swh_space *s, const swh_kick_params *K,
+                                          const swh_hydro_params *P, double dt_kick_mesh_grav);
+SWH_API swh_status swh_space_kick2_linked(swh_space *s, const swh_kick_params *K,
+                                          const swh_hydro_params *P, double dt_kick_mesh_grav);
+SWH_API swh_status swh_space_timestep_linked(swh_space *s, const swh_timestep_params *T,
+                                             const swh_hydro_params *P);
+SWH_API swh_status swh_space_end_step_linked(swh_space *s, const swh_kick_params *K2,
+                                             const swh_timestep_params *T,
+                                             const swh_kick_params *K1, const swh_hydro_params *P,
+                                             double dt_kick_mesh2, double dt_kick_mesh1);
+/* Device time of the last launch of each linked stage (ms, HIP events on the
+ * stream the stage runs on; waits for them): ms[0..3) = pull, push, the last
+ * linked kick1 / kick2 / timestep / end_step. -1 for a stage not yet run. */
+SWH_API swh_status swh_space_link_times(swh_space *s, float *ms);
 
 #ifdef __cplusplus
 }

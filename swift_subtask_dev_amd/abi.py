@@ -97,7 +97,7 @@ XPART_DTYPE = np.dtype(
 )
 
 # include/swifthip.h SWH_ABI_VERSION: the ctypes layouts below are written for it
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 NUM_TIME_BINS = 56  # src/timeline.h:36
 TIME_BIN_INHIBITED = NUM_TIME_BINS + 2
@@ -358,6 +358,19 @@ def default_gtimestep_params(**kw) -> GTimestepParams:
     for k, v in kw.items():
         setattr(T, k, v)
     return T
+
+
+# swh_push_params.what (swh_space_push_gparts)
+PUSH_X, PUSH_V_FULL, PUSH_TIME_BIN = 1, 2, 4
+
+
+class PushParams(C.Structure):
+    """swh_push_params: what a linked space writes into its gas gparts."""
+
+    _fields_ = [("what", C.c_uint32), ("periodic", C.c_int32), ("dim", C.c_double * 3)]
+
+    def __init__(self, what=0, periodic=0, dim=(1.0, 1.0, 1.0)):
+        super().__init__(int(what), int(periodic), (C.c_double * 3)(*dim))
 
 
 class GCell(C.Structure):

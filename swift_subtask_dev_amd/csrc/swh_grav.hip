@@ -1368,6 +1368,7 @@ swh_status swh_gspace_destroy(swh_gspace* g) {
   mesh_release(g);
   gtree_release(g);
   gstep_release(g);
+  couple_release(g);
   (void)hipStreamDestroy(g->stream);
   delete g;
   return SWH_OK;
@@ -1382,6 +1383,7 @@ swh_status swh_gspace_upload(swh_gspace* g, const void* gparts, int64_t count,
   GLayout L;
   SWH_TRY(make_glayout(GL, &L));
   SWH_HIP(hipSetDevice(g->ctx->device));
+  couple_unlink(g);  // the records a space was linked to are gone
   g->layout = L;
   g->n = count;
   g->uploaded = true;

@@ -198,6 +198,19 @@ struct swh_space {
   hipEvent_t step_event = nullptr;  // behind the last record copy
   bool step_pending = false;  // a record copy is queued and not yet read (vfull_max)
   bool step_has_ts = false;   // the record holds a timestep's fields
+  // gas <-> gpart link (swh_couple.hip): the gspace whose gas gparts name this
+  // space's parts, their a_grav and a_grav_mesh in sorted order (float4, filled
+  // by swh_space_pull_gravity, void after a rebuild), the check's scratch
+  swh_gspace* link = nullptr;
+  int64_t n_linked = 0;
+  swh::DevBuf gp_agrav_s, gp_amesh_s;
+  bool gp_pulled = false;
+  swh::DevBuf link_mark, link_cnt;  // i32[n] parts named, u32[4] the check's counts
+  hipEvent_t link_event = nullptr;  // recorded on this space's stream for the gspace's
+  // HIP events around the last pull, push and linked kick / timestep launch
+  // (swh_space_link_times)
+  hipEvent_t link_tev[3][2] = {};
+  bool link_timed[3] = {false, false, false};
   // grid
   swh::DevBuf cell_start;  // int32[ncell+1], indexed by Morton rank
   swh::DevBuf cell_rank;   // int32[ncell]: linear cell -> Morton rank
@@ -324,6 +337,9 @@ struct swh_gspace {
   // end_force, kick / timestep / end_step (swh_gspace_step_times)
   hipEvent_t gstep_tev[4][2] = {};
   bool gstep_timed[4] = {false, false, false, false};
+  // gas <-> gpart link (swh_couple.hip)
+  swh_space* link = nullptr;
+  hipEvent_t link_event = nullptr;  // recorded on this gspace's stream for the space's
 };
 
 namespace swh {
@@ -335,4 +351,13 @@ void gstep_release(swh_gspace* g);  // swh_gkick.hip: the step record's buffers 
 // leaf_of is filled on the device (gtree_fill_leaf_of), nothing O(N) on the host.
 swh_status gtree_install(swh_gspace* g, const swh_gcell* cells, int32_t ncells, bool device_built);
 swh_status gtree_fill_leaf_of(swh_gspace* g, int32_t ncells);  // swh_gtree.hip
+// swh_couple.hip: drop the link of either object (both sides forget it); the
+// _release calls also free the link's buffers and event (the destroy calls)
+void couple_unlink(swh_space* s);
+void couple_unlink(swh_gspace* g);
+void couple_release(swh_space* s);
+void couple_release(swh_gspace* g);
+enum { LT_PULL = 0, LT_PUSH, LT_STEP };
+swh_status couple_stage_begin(swh_space* s, int stage, hipStream_t st);
+swh_status couple_stage_end(swh_space* s, int stage, hipStream_t st);
 }

@@ -12,10 +12,16 @@
 // flag) once, grid-stride, and reduces the step's record per wave, then per
 // block in LDS, then with one integer atomic per block and field: the record
 // does not depend on the order of the blocks.
+// A fourth flag, LK, is the same kernel for a space linked to a gspace
+// (swh_couple.hip): a linked particle's gravity comes from the two arrays
+// swh_space_pull_gravity filled (its gpart's a_grav and a_grav_mesh), with the
+// mesh kick, and kick1 leaves xp->a_grav for the drift. The entries without a
+// link instantiate it false.
 #include <cfloat>
 #include <cmath>
 #include <cstring>
 
+#include "swh_couple.h"
 #include "swh_internal.h"
 #include "swh_physics.h"
 #include "swh_space.h"
@@ -49,11 +55,28 @@ struct TimestepDev {
 // record slots (u64 each, all reduced by atomicMax / atomicAdd from zero)
 enum { REC_END_MIN = 0, REC_END_MAX, REC_BEG_MAX, REC_UPDATED, REC_BELOW, REC_VMAX, REC_SLOTS = 8 };
 
-// kick_part (src/kick.h:214-280) + SPHENIX hydro_kick_extra (hydro.h:1103-1130)
-// over a half-step of bin `bin`. vf: v_full, u_full; ac: a_hydro, u_dt.
+// the row of the per-bin half-step tables for time bin `bin`
+__device__ __forceinline__ int kick_bin(int bin) {
+  return bin < 0 ? 0 : (bin >= kBinTable ? kBinTable - 1 : bin);
+}
+
+// SPHENIX hydro_kick_extra (hydro.h:1103-1130): u_full, and u_dt = 0 at the
+// energy floor
+__device__ __forceinline__ void kick_part_therm(const KickDev& K, int b, float4& vf, float4& ac) {
+  const float delta_u = ac.w * (float)K.dt_therm[b];
+  vf.w = fmaxf(vf.w + delta_u, 0.5f * vf.w);  // at most a factor 2 down
+  const float energy_min = fmaxf(K.min_u, 0.f);  // entropy floor NONE: floor_u = 0
+  if (vf.w < energy_min) {
+    vf.w = energy_min;
+    ac.w = 0.f;
+  }
+}
+
+// kick_part (src/kick.h:214-280) + hydro_kick_extra over a half-step of bin
+// `bin`. vf: v_full, u_full; ac: a_hydro, u_dt.
 __device__ __forceinline__ void kick_part(const KickDev& K, int bin, float4& vf, float4& ac,
                                           const float4& ag, bool hasg) {
-  const int b = bin < 0 ? 0 : (bin >= kBinTable ? kBinTable - 1 : bin);
+  const int b = kick_bin(bin);
   const double dt_hydro = K.dt_hydro[b], dt_grav = K.dt_grav[b];
   // float += float * double
   vf.x = (float)((double)vf.x + (double)ac.x * dt_hydro);
@@ -64,32 +87,47 @@ __device__ __forceinline__ void kick_part(const KickDev& K, int bin, float4& vf,
     vf.y = (float)((double)vf.y + (double)ag.y * dt_grav);
     vf.z = (float)((double)vf.z + (double)ag.z * dt_grav);
   }
-  const float delta_u = ac.w * (float)K.dt_therm[b];
-  vf.w = fmaxf(vf.w + delta_u, 0.5f * vf.w);  // at most a factor 2 down
-  const float energy_min = fmaxf(K.min_u, 0.f);  // entropy floor NONE: floor_u = 0
-  if (vf.w < energy_min) {
-    vf.w = energy_min;
-    ac.w = 0.f;
-  }
+  kick_part_therm(K, b, vf, ac);
+}
+
+// kick_part for a particle linked to its gpart (swh_couple.h): the tree and
+// the mesh acceleration of the gpart, the mesh kick always added
+__device__ __forceinline__ void kick_part_lk(const KickDev& K, int bin, float4& vf, float4& ac,
+                                             const float4& ga, const float4& gm, double dt_mesh) {
+  const int b = kick_bin(bin);
+  float v[3] = {vf.x, vf.y, vf.z};
+  const float ah[3] = {ac.x, ac.y, ac.z}, a[3] = {ga.x, ga.y, ga.z}, m[3] = {gm.x, gm.y, gm.z};
+  kick_part_linked(v, ah, a, m, K.dt_hydro[b], K.dt_grav[b], dt_mesh);
+  vf.x = v[0], vf.y = v[1], vf.z = v[2];
+  kick_part_therm(K, b, vf, ac);
 }
 
 // get_part_timestep (src/timestep.h:141-222): hydro_compute_timestep
 // (hydro.h:464-476), gravity_compute_timestep_self for particles with a gpart,
 // the h-change limit, the engine's bounds. Returns the step in float, as the
 // reference carries it; *below: the particle wanted less than dt_min.
+// LK: ag / gm are the gpart's a_grav and a_grav_mesh (swh_couple.h's norm).
+template <bool LK = false>
 __device__ __forceinline__ float part_timestep(const TimestepDev& T, float h, float v_sig,
                                                float h_dt, const float4& ac, const float4& ag,
-                                               bool hasg, bool* below) {
+                                               bool hasg, bool* below,
+                                               const float4& gm = make_float4(0.f, 0.f, 0.f, 0.f)) {
   float new_dt = (float)(((double)T.cfl_factor * T.a * (double)h) /
                          (T.a_factor_sound_speed * (double)v_sig));
   if (hasg && T.grav_dt_factor > 0.f) {
-    float ax = (float)((double)ag.x * T.a_factor_grav_accel);
-    float ay = (float)((double)ag.y * T.a_factor_grav_accel);
-    float az = (float)((double)ag.z * T.a_factor_grav_accel);
-    ax = (float)((double)ax + (double)ac.x * T.a_factor_hydro_accel);
-    ay = (float)((double)ay + (double)ac.y * T.a_factor_hydro_accel);
-    az = (float)((double)az + (double)ac.z * T.a_factor_hydro_accel);
-    const float ac2 = ax * ax + ay * ay + az * az;
+    float ac2;
+    if (LK) {
+      const float a[3] = {ag.x, ag.y, ag.z}, m[3] = {gm.x, gm.y, gm.z}, ah[3] = {ac.x, ac.y, ac.z};
+      ac2 = linked_accel_norm2(a, m, ah, T.a_factor_grav_accel, T.a_factor_hydro_accel);
+    } else {
+      float ax = (float)((double)ag.x * T.a_factor_grav_accel);
+      float ay = (float)((double)ag.y * T.a_factor_grav_accel);
+      float az = (float)((double)ag.z * T.a_factor_grav_accel);
+      ax = (float)((double)ax + (double)ac.x * T.a_factor_hydro_accel);
+      ay = (float)((double)ay + (double)ac.y * T.a_factor_hydro_accel);
+      az = (float)((double)az + (double)ac.z * T.a_factor_hydro_accel);
+      ac2 = ax * ax + ay * ay + az * az;
+    }
     const float ac_inv = ac2 > 0.f ? 1.f / sqrtf(ac2) : FLT_MAX;
     new_dt = fminf(new_dt, sqrtf(T.grav_dt_factor * ac_inv));
   }
@@ -115,12 +153,24 @@ __device__ __forceinline__ unsigned int wave_sum_u(unsigned int v) {
   return v;
 }
 
-template <bool K2, bool TS, bool K1>
+// The link's arrays (LK): the gparts' a_grav and a_grav_mesh (sorted, pulled),
+// xp->a_grav for kick1 to write, the mesh kicks of this call.
+struct LinkDev {
+  const float4* gp_agrav;
+  const float4* gp_amesh;
+  float4* xp_agrav;
+  double dt_mesh2, dt_mesh1;
+};
+
+// LK launches pass agrav = nullptr: xp->a_grav is only written there, through
+// lk.xp_agrav.
+template <bool K2, bool TS, bool K1, bool LK>
 __global__ __launch_bounds__(256) void step_kernel(SoA a, float4* __restrict__ vfull,
                                                    const float4* __restrict__ agrav,
                                                    const int8_t* __restrict__ hasg, int64_t n,
                                                    KickDev k2, TimestepDev T, KickDev k1,
-                                                   unsigned long long* __restrict__ rec) {
+                                                   unsigned long long* __restrict__ rec,
+                                                   LinkDev lk) {
   __shared__ long long sm_t[3][4];
   __shared__ unsigned int sm_c[2][4];
   __shared__ float sm_v[4];
@@ -137,11 +187,23 @@ __global__ __launch_bounds__(256) void step_kernel(SoA a, float4* __restrict__ v
     if (a.perm[s] < a.n_owned) {  // foreign halo copies are never kicked
       float4 ac = a.acc[s];
       const float u_dt_in = ac.w;
-      const float4 ag = agrav[s];
-      const bool hg = hasg[s] != 0;
+      const bool hg = hasg[s] != 0;  // LK: linked to a gpart
+      float4 ag, gm = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (LK) {
+        ag = gm;
+        if (hg) {
+          ag = lk.gp_agrav[s];
+          gm = lk.gp_amesh[s];
+        }
+      } else {
+        ag = agrav[s];
+      }
       bool moved = false;
       if (K2 && bin <= k2.max_active_bin) {
-        kick_part(k2, bin, vf, ac, ag, hg);
+        if (LK && hg)
+          kick_part_lk(k2, bin, vf, ac, ag, gm, lk.dt_mesh2);
+        else
+          kick_part(k2, bin, vf, ac, ag, hg);
         moved = true;
         // hydro_reset_predicted_values (hydro.h:966-991)
         float4 vm = a.vm[s];
@@ -164,8 +226,8 @@ __global__ __launch_bounds__(256) void step_kernel(SoA a, float4* __restrict__ v
         long long ti_end, ti_beg;
         if (bin <= T.max_active_bin) {
           bool below;
-          const float new_dt = part_timestep(T, (float)a.pos[s].w, a.grad[s].x, a.hdt[s], ac, ag,
-                                             hg, &below);
+          const float new_dt = part_timestep<LK>(T, (float)a.pos[s].w, a.grad[s].x, a.hdt[s], ac,
+                                                 ag, hg, &below, gm);
           const int64_t new_dti =
               make_integer_timestep(new_dt, bin, a.mintb[s], T.ti_current, T.time_base_inv);
           bin = get_time_bin(new_dti);
@@ -184,7 +246,16 @@ __global__ __launch_bounds__(256) void step_kernel(SoA a, float4* __restrict__ v
         beg_max = ti_beg > beg_max ? ti_beg : beg_max;
       }
       if (K1 && bin <= k1.max_active_bin) {  // part_is_starting, on the new bin
-        kick_part(k1, bin, vf, ac, ag, hg);
+        if (LK && hg) {
+          kick_part_lk(k1, bin, vf, ac, ag, gm, lk.dt_mesh1);
+          // runner_do_kick1: the drift's acceleration
+          float x[3];
+          const float g3[3] = {ag.x, ag.y, ag.z}, m3[3] = {gm.x, gm.y, gm.z};
+          linked_xp_a_grav(x, g3, m3);
+          lk.xp_agrav[s] = make_float4(x[0], x[1], x[2], 0.f);
+        } else {
+          kick_part(k1, bin, vf, ac, ag, hg);
+        }
         moved = true;
       }
       if (moved) {
@@ -302,13 +373,22 @@ static swh_status step_ready(swh_space* s, const char* what) {
   return SWH_OK;
 }
 
-template <bool K2, bool TS, bool K1>
+template <bool K2, bool TS, bool K1, bool LK = false>
 static swh_status launch_step(swh_space* s, const swh_kick_params* k2,
                               const swh_timestep_params* T, const swh_kick_params* k1,
-                              const swh_hydro_params* P, const char* what) {
+                              const swh_hydro_params* P, const char* what, double dt_mesh2 = 0.,
+                              double dt_mesh1 = 0.) {
   if (!s || !P || (K2 && !k2) || (TS && !T) || (K1 && !k1)) return SWH_ERR_ARG;
+  if (LK && !s->link) {
+    set_error("swh_space_link_gspace must precede %s", what);
+    return SWH_ERR_STATE;
+  }
   if (s->n == 0) return SWH_OK;
   SWH_TRY(step_ready(s, what));
+  if (LK && !s->gp_pulled) {
+    set_error("%s: no swh_space_pull_gravity since the last rebuild or upload", what);
+    return SWH_ERR_STATE;
+  }
   SWH_HIP(hipSetDevice(s->ctx->device));
   hipStream_t st = s->stream;
   SWH_TRY(space_ensure_xsorted(s));
@@ -330,10 +410,18 @@ static swh_status launch_step(swh_space* s, const swh_kick_params* k2,
   fill_kick(K1 ? k1 : &kNoKick, &d1);
   if (TS) fill_timestep(T, P, &dt);
   const int grid = (int)std::min<int64_t>((s->n + 255) / 256, 4 * kReduceBlocks);
-  hipLaunchKernelGGL((step_kernel<K2, TS, K1>), dim3(grid), dim3(256), 0, st, soa_of(s),
-                     s->vfull_s.as<float4>(), s->agrav_s.as<const float4>(),
-                     s->hasg_s.as<const int8_t>(), s->n, d2, dt, d1, rec);
+  LinkDev lk{nullptr, nullptr, nullptr, dt_mesh2, dt_mesh1};
+  if (LK) {
+    lk.gp_agrav = s->gp_agrav_s.as<const float4>();
+    lk.gp_amesh = s->gp_amesh_s.as<const float4>();
+    lk.xp_agrav = s->agrav_s.as<float4>();
+  }
+  if (LK) SWH_TRY(couple_stage_begin(s, LT_STEP, st));
+  hipLaunchKernelGGL((step_kernel<K2, TS, K1, LK>), dim3(grid), dim3(256), 0, st, soa_of(s),
+                     s->vfull_s.as<float4>(), LK ? nullptr : s->agrav_s.as<const float4>(),
+                     s->hasg_s.as<const int8_t>(), s->n, d2, dt, d1, rec, lk);
   SWH_HIP(hipGetLastError());
+  if (LK) SWH_TRY(couple_stage_end(s, LT_STEP, st));
   SWH_HIP(hipMemcpyAsync(s->step_host.ptr, rec, REC_SLOTS * sizeof(unsigned long long),
                          hipMemcpyDeviceToHost, st));
   SWH_HIP(hipEventRecord(s->step_event, st));
@@ -386,6 +474,32 @@ swh_status swh_space_end_step(swh_space* s, const swh_kick_params* K2,
                               const swh_timestep_params* T, const swh_kick_params* K1,
                               const swh_hydro_params* P) {
   return launch_step<true, true, true>(s, K2, T, K1, P, "swh_space_end_step");
+}
+
+swh_status swh_space_kick1_linked(swh_space* s, const swh_kick_params* K,
+                                  const swh_hydro_params* P, double dt_kick_mesh_grav) {
+  return launch_step<false, false, true, true>(s, nullptr, nullptr, K, P,
+                                               "swh_space_kick1_linked", 0., dt_kick_mesh_grav);
+}
+
+swh_status swh_space_kick2_linked(swh_space* s, const swh_kick_params* K,
+                                  const swh_hydro_params* P, double dt_kick_mesh_grav) {
+  return launch_step<true, false, false, true>(s, K, nullptr, nullptr, P,
+                                               "swh_space_kick2_linked", dt_kick_mesh_grav, 0.);
+}
+
+swh_status swh_space_timestep_linked(swh_space* s, const swh_timestep_params* T,
+                                     const swh_hydro_params* P) {
+  return launch_step<false, true, false, true>(s, nullptr, T, nullptr, P,
+                                               "swh_space_timestep_linked");
+}
+
+swh_status swh_space_end_step_linked(swh_space* s, const swh_kick_params* K2,
+                                     const swh_timestep_params* T, const swh_kick_params* K1,
+                                     const swh_hydro_params* P, double dt_kick_mesh2,
+                                     double dt_kick_mesh1) {
+  return launch_step<true, true, true, true>(s, K2, T, K1, P, "swh_space_end_step_linked",
+                                             dt_kick_mesh2, dt_kick_mesh1);
 }
 
 swh_status swh_space_step_result(swh_space* s, swh_step_result* out) {

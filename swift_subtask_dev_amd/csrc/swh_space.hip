@@ -705,6 +705,12 @@ swh_status space_xparts_to_caller(swh_space* s) {
                      s->perm.as<const int>(), s->vfull_s.as<const float4>(), s->n,
                      s->vfull_c.as<float4>());
   SWH_HIP(hipGetLastError());
+  if (s->link) {  // a linked kick1 wrote xp->a_grav into the sorted copy
+    hipLaunchKernelGGL(xunsort_kernel, dim3((int)((s->n + 255) / 256)), dim3(256), 0, s->stream,
+                       s->perm.as<const int>(), s->agrav_s.as<const float4>(), s->n,
+                       s->agrav_c.as<float4>());
+    SWH_HIP(hipGetLastError());
+  }
   return SWH_OK;
 }
 
@@ -743,6 +749,7 @@ swh_status swh_space_destroy(swh_space* s) {
                     &s->iperm, &s->vfull_s, &s->agrav_s, &s->hasg_s, &s->list_xd0,
                     &s->step_rec};
   for (DevBuf* b : bufs) b->release();
+  couple_release(s);
   s->step_host.release();
   if (s->step_event) (void)hipEventDestroy(s->step_event);
   s->hstage.release();
@@ -919,6 +926,7 @@ swh_status swh_space_upload_parts(swh_space* s, const void* parts, int64_t count
   Layout L;
   SWH_TRY(make_layout(PL, &L));
   SWH_HIP(hipSetDevice(s->ctx->device));
+  couple_unlink(s);  // the parts the gas gparts named are gone
   s->layout = L;
   s->n = count;
   s->n_owned = count;
@@ -971,6 +979,7 @@ swh_status swh_space_download_parts(swh_space* s, void* parts, const swh_part_la
 
 swh_status swh_space_set_owned(swh_space* s, int64_t n_owned) {
   if (!s || n_owned < 0 || n_owned > s->n) return SWH_ERR_ARG;
+  if (n_owned < s->n) couple_unlink(s);  // the link covers one device's particles only
   s->n_owned = n_owned;
   s->list_valid = false;  // the lists hold owned (active) particles only
   return SWH_OK;
@@ -1024,6 +1033,7 @@ swh_status swh_space_rebuild(swh_space* s, const swh_hydro_params* P, double min
   // first and are gathered again by the next drift or kick
   SWH_TRY(space_xparts_to_caller(s));
   s->xsorted_valid = false;
+  s->gp_pulled = false;  // the pulled accelerations were in the old order
   // 1. bounding box + max h
   const int nb = 512;
   SWH_TRY(s->scan_tmp.reserve(nb * 8 * sizeof(double)));

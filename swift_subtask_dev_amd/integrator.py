@@ -158,7 +158,89 @@ class Integrator:
         return self.ti_current * self.time_base
 
 
-class NBodyIntegrator:
+class _GravityDriver:
+    """What NBodyIntegrator and CoupledIntegrator share on the gspace side: the
+    tree build, the gravity stages and the mesh schedule of engine.c:3528-3550
+    without the RMS-displacement term. Expects gs, G, GT (abi.GTimestepParams),
+    time_base, cdim, split_size, max_depth, box, const_G, mesh, periodic,
+    ti_current and max_active_bin on the object."""
+
+    def _reset_gravity(self):
+        self.tops = None
+        self._pairs = None
+        self.potential_normalisation = 0.0
+        self.mesh_ti_beg = self.mesh_ti_end = -1
+        self.mesh_kicks = 0  # half mesh kicks given to the gparts so far
+
+    def _gkick_params(self, dt_mesh: float = 0.0) -> abi.GKickParams:
+        K = abi.GKickParams()
+        K.ti_current = self.ti_current
+        K.time_base = self.time_base
+        K.max_active_bin = self.max_active_bin
+        K.dt_kick_mesh_grav = dt_mesh
+        if dt_mesh != 0.0:
+            self.mesh_kicks += 1
+        return K
+
+    def _next_mesh_step(self) -> int:
+        """engine.c:3528-3550 without the RMS term: the length of the mesh
+        step that starts at ti_current."""
+        new_dti = int(self.GT.dt_max * self.GT.time_base_inv)
+        line = MAX_NR_TIMESTEPS
+        while new_dti < line:
+            line //= 2
+        new_dti = line
+        current = self.mesh_ti_end - self.mesh_ti_beg if self.mesh_ti_end > 0 else MAX_NR_TIMESTEPS
+        if new_dti > current and (MAX_NR_TIMESTEPS - self.ti_current) % new_dti > 0:
+            new_dti = current
+        return new_dti
+
+    def _mesh_step_ends(self) -> bool:
+        return bool(self.mesh) and self.ti_current == self.mesh_ti_end
+
+    def _first_mesh_kick(self) -> float:
+        """The mesh half-kick of init_step's kick1 (0 without a mesh); starts
+        the first mesh step."""
+        if not self.mesh:
+            return 0.0
+        self.mesh_ti_beg = 0
+        self.mesh_ti_end = self._next_mesh_step()
+        return (self.mesh_ti_end // 2) * self.time_base
+
+    def _mesh_kicks_here(self):
+        """(kick2's, kick1's) mesh half-kick at ti_current: half the mesh step
+        that ends here and half the one that starts, (0, 0) elsewhere."""
+        dt2 = dt1 = 0.0
+        if self._mesh_step_ends():
+            dt2 = ((self.mesh_ti_end - self.mesh_ti_beg) // 2) * self.time_base
+            new_dti = self._next_mesh_step()
+            self.mesh_ti_beg = self.ti_current
+            self.mesh_ti_end = self.ti_current + new_dti
+            dt1 = (new_dti // 2) * self.time_base
+        return dt2, dt1
+
+    def _set_potential_normalisation(self, g: np.ndarray, live: np.ndarray):
+        if self.mesh and self.periodic:
+            # runner_others.c:722-726
+            total_mass = float(g["mass"][live].astype(np.float64).sum())
+            r_s = float(self.mesh["r_s"])
+            self.potential_normalisation = 4.0 * np.pi * total_mass * r_s * r_s / self.box ** 3
+
+    def _build(self):
+        _, tops = self.gs.build_tree(self.cdim, self.split_size, self.box, self.max_depth)
+        if self.tops is None or not np.array_equal(tops, self.tops):
+            self.tops = tops
+            self._pairs = ics.top_level_pairs(tops)
+
+    def gravity(self):
+        self.gs.init_grav(self.max_active_bin)
+        if self.mesh and (self.ti_current == 0 or self._mesh_step_ends()):
+            self.gs.pm_mesh(int(self.mesh["N"]), self.box, float(self.mesh["r_s"]), self.const_G)
+        self.gs.tree(self.G, self.tops, self._pairs, stats=False)
+        self.gs.end_force(self.const_G, self.potential_normalisation, self.periodic)
+
+
+class NBodyIntegrator(_GravityDriver):
     """A multi-step, multi-time-bin driver over one GravSpace: the gparts stay
     on the device from the first upload on (non-cosmological).
 
@@ -191,7 +273,7 @@ class NBodyIntegrator:
             raise ValueError("time_base (time per tick) must be positive")
         self.gs = gspace
         self.G = G
-        self.T = T
+        self.T = self.GT = T
         self.time_base = float(time_base)
         self.T.time_base_inv = 1.0 / self.time_base
         self.cdim, self.split_size, self.max_depth = int(cdim), int(split_size), int(max_depth)
@@ -202,11 +284,7 @@ class NBodyIntegrator:
         self.ti_current = 0
         self.max_active_bin = abi.NUM_TIME_BINS
         self.result = None
-        self.tops = None
-        self._pairs = None
-        self.potential_normalisation = 0.0
-        self.mesh_ti_beg = self.mesh_ti_end = -1
-        self.mesh_kicks = 0  # half mesh kicks given so far
+        self._reset_gravity()
 
     # -- engine scalars at ti_current -------------------------------------
     def _update_scalars(self):
@@ -214,34 +292,7 @@ class NBodyIntegrator:
         self.T.max_active_bin = self.max_active_bin
         self.T.ti_current = self.ti_current
 
-    def _kick_params(self, dt_mesh: float = 0.0) -> abi.GKickParams:
-        K = abi.GKickParams()
-        K.ti_current = self.ti_current
-        K.time_base = self.time_base
-        K.max_active_bin = self.max_active_bin
-        K.dt_kick_mesh_grav = dt_mesh
-        if dt_mesh != 0.0:
-            self.mesh_kicks += 1
-        return K
-
-    def _next_mesh_step(self) -> int:
-        """engine.c:3528-3550 without the RMS term: the length of the mesh
-        step that starts at ti_current."""
-        new_dti = int(self.T.dt_max * self.T.time_base_inv)
-        line = MAX_NR_TIMESTEPS
-        while new_dti < line:
-            line //= 2
-        new_dti = line
-        current = self.mesh_ti_end - self.mesh_ti_beg if self.mesh_ti_end > 0 else MAX_NR_TIMESTEPS
-        if new_dti > current and (MAX_NR_TIMESTEPS - self.ti_current) % new_dti > 0:
-            new_dti = current
-        return new_dti
-
-    def _build(self):
-        _, tops = self.gs.build_tree(self.cdim, self.split_size, self.box, self.max_depth)
-        if self.tops is None or not np.array_equal(tops, self.tops):
-            self.tops = tops
-            self._pairs = ics.top_level_pairs(tops)
+    _kick_params = _GravityDriver._gkick_params
 
     # -- the entry points -----------------------------------------------------
     def init_step(self, gparts: np.ndarray) -> dict:
@@ -255,21 +306,12 @@ class NBodyIntegrator:
         self.mesh_ti_beg = self.mesh_ti_end = -1
         self.mesh_kicks = 0
         self._update_scalars()
-        if self.mesh and self.periodic:
-            # runner_others.c:722-726
-            total_mass = float(g["mass"][live].astype(np.float64).sum())
-            r_s = float(self.mesh["r_s"])
-            self.potential_normalisation = 4.0 * np.pi * total_mass * r_s * r_s / self.box ** 3
+        self._set_potential_normalisation(g, live)
         self.gs.upload(g)
         self._build()
         self.gravity()
         self.gs.timestep(self.T)
-        dt_mesh = 0.0
-        if self.mesh:
-            self.mesh_ti_beg = 0
-            self.mesh_ti_end = self._next_mesh_step()
-            dt_mesh = (self.mesh_ti_end // 2) * self.time_base
-        self.gs.kick1(self._kick_params(dt_mesh))
+        self.gs.kick1(self._kick_params(self._first_mesh_kick()))
         self.result = self.gs.step_result()
         return self.result
 
@@ -286,24 +328,8 @@ class NBodyIntegrator:
         self._build()
         return dt
 
-    def _mesh_step_ends(self) -> bool:
-        return bool(self.mesh) and self.ti_current == self.mesh_ti_end
-
-    def gravity(self):
-        self.gs.init_grav(self.max_active_bin)
-        if self.mesh and (self.ti_current == 0 or self._mesh_step_ends()):
-            self.gs.pm_mesh(int(self.mesh["N"]), self.box, float(self.mesh["r_s"]), self.const_G)
-        self.gs.tree(self.G, self.tops, self._pairs, stats=False)
-        self.gs.end_force(self.const_G, self.potential_normalisation, self.periodic)
-
     def end_step(self) -> dict:
-        dt2 = dt1 = 0.0
-        if self._mesh_step_ends():
-            dt2 = ((self.mesh_ti_end - self.mesh_ti_beg) // 2) * self.time_base
-            new_dti = self._next_mesh_step()
-            self.mesh_ti_beg = self.ti_current
-            self.mesh_ti_end = self.ti_current + new_dti
-            dt1 = (new_dti // 2) * self.time_base
+        dt2, dt1 = self._mesh_kicks_here()
         self.gs.end_step(self._kick_params(dt2), self.T, self._kick_params(dt1))
         self.result = self.gs.step_result()
         return self.result
@@ -311,6 +337,182 @@ class NBodyIntegrator:
     def step(self) -> dict:
         self.drift_to_next()
         self.gravity()
+        return self.end_step()
+
+    @property
+    def time(self) -> float:
+        return self.ti_current * self.time_base
+
+
+class CoupledIntegrator(_GravityDriver):
+    """Self-gravitating gas: one HydroSpace and one GravSpace stepped together
+    (non-cosmological), the gas linked to its gas gparts on the device
+    (swh_space_link_gspace). Nothing leaves the device after init_step's
+    uploads: the gas reads its gravity from the linked records
+    (pull_gravity) and writes x, v_full and time_bin back into them
+    (push_gparts), as SWIFT's part loops do through p->gpart.
+
+        init_step()  every live particle active in bin 0; link, rebuild, tree
+                     build; gravity; pull; the hydro chain; both time steps;
+                     push time_bin; both first half-kicks; push v_full
+        step()       ti_current = the smaller ti_end_min of the two records;
+                     drift the space (with its displacement-triggered rebuild)
+                     and the gspace; push x; tree build; gravity on the
+                     gspace's stream and the hydro chain on the space's; pull;
+                     end_step_linked and the gspace's end_step; push v_full
+                     and time_bin; the two records
+
+    P, T: the hydro side's abi.HydroParams / abi.TimestepParams (T's
+    grav_dt_factor > 0 gives the gas its gravity time-step condition); G, GT:
+    the gravity side's abi.GravParams / abi.GTimestepParams. Both sides share
+    dt_max: the mesh step (NBodyIntegrator's schedule) must bound every
+    particle's step. The two record reads are the step's only host waits
+    beyond those the hydro chain already has."""
+
+    def __init__(self, space, gspace, P: abi.HydroParams, T: abi.TimestepParams,
+                 G: abi.GravParams, GT: abi.GTimestepParams, time_base: float, cdim: int,
+                 split_size: int = 64, max_depth: int = 12, box: float = 1.0,
+                 const_G: float = 1.0, min_u: float = 0.0, max_rel_dx: float = 0.1,
+                 mesh: dict = None):
+        if not time_base or time_base <= 0:
+            raise ValueError("time_base (time per tick) must be positive")
+        if T.dt_max != GT.dt_max:
+            raise ValueError(f"the gas and the gparts need one dt_max: {T.dt_max} != {GT.dt_max}")
+        self.sp, self.gs = space, gspace
+        self.P, self.T, self.G, self.GT = P, T, G, GT
+        self.time_base = float(time_base)
+        self.P.time_base = self.time_base
+        self.T.time_base_inv = self.GT.time_base_inv = 1.0 / self.time_base
+        self.cdim, self.split_size, self.max_depth = int(cdim), int(split_size), int(max_depth)
+        self.box = float(box)
+        self.const_G = float(const_G)
+        self.min_u = float(min_u)
+        self.max_rel_dx = float(max_rel_dx)
+        self.mesh = dict(mesh) if mesh else None
+        self.periodic = bool(G.periodic)
+        self.ti_current = 0
+        self.max_active_bin = abi.NUM_TIME_BINS
+        self.result = self.result_gas = self.result_gparts = None
+        self.rebuilds = 0
+        self.gas_mesh_kicks = 0  # half mesh kicks given to the gas so far
+        self.n_linked = 0
+        self.chain = None
+        self._reset_gravity()
+
+    def _update_scalars(self):
+        self.P.max_active_bin = self.max_active_bin
+        self.T.ti_current = self.ti_current
+        self.G.max_active_bin = self.max_active_bin
+        self.GT.max_active_bin = self.max_active_bin
+        self.GT.ti_current = self.ti_current
+
+    def _kick_params(self) -> abi.KickParams:
+        K = abi.KickParams()
+        K.ti_current = self.ti_current
+        K.time_base = self.time_base
+        K.max_active_bin = self.max_active_bin
+        K.min_u = self.min_u
+        return K
+
+    @staticmethod
+    def merge_records(gas: dict, gparts: dict) -> dict:
+        """One record of the step from the space's and the gspace's."""
+        return {"ti_end_min": min(gas["ti_end_min"], gparts["ti_end_min"]),
+                "ti_end_max": max(gas["ti_end_max"], gparts["ti_end_max"]),
+                "ti_beg_max": max(gas["ti_beg_max"], gparts["ti_beg_max"]),
+                "n_updated": gas["n_updated"],
+                "g_updated": gas["n_updated"] + gparts["n_updated"],
+                "n_below_dt_min": gas["n_below_dt_min"] + gparts["n_below_dt_min"],
+                "vfull_max": max(gas["vfull_max"], gparts["vfull_max"])}
+
+    def _read_records(self) -> dict:
+        self.result_gas = self.sp.step_result()
+        self.result_gparts = self.gs.step_result()
+        self.result = self.merge_records(self.result_gas, self.result_gparts)
+        return self.result
+
+    def _push(self, **what):
+        self.sp.push_gparts(periodic=self.periodic, dim=(self.box,) * 3, **what)
+
+    # -- the entry points -----------------------------------------------------
+    def init_step(self, parts: np.ndarray, xparts: np.ndarray, gparts: np.ndarray) -> dict:
+        """The only uploads of the run, then the first forces, time steps and
+        half-kicks. Every live particle starts in time bin 0."""
+        p, g = abi.copy_parts(parts), abi.copy_parts(gparts)
+        for a in (p, g):
+            alive = a["time_bin"] != abi.TIME_BIN_INHIBITED
+            a["time_bin"] = np.where(alive, 0, a["time_bin"]).astype(np.int8)
+        self.ti_current = 0
+        self.max_active_bin = abi.NUM_TIME_BINS
+        self.mesh_ti_beg = self.mesh_ti_end = -1
+        self.mesh_kicks = self.gas_mesh_kicks = 0
+        self._update_scalars()
+        self._set_potential_normalisation(g, g["time_bin"] != abi.TIME_BIN_INHIBITED)
+        self.sp.upload(p)
+        self.sp.upload_xparts(xparts)
+        self.gs.upload(g)
+        self.n_linked = self.sp.link(self.gs)
+        self.sp.rebuild(self.P)
+        self._build()
+        self.gravity()
+        self.sp.pull_gravity()
+        self.chain = self.sp.hydro_step(self.P)
+        self.sp.timestep_linked(self.T, self.P)
+        self.gs.timestep(self.GT)
+        self._push(time_bin=True)
+        dt_mesh = self._first_mesh_kick()
+        self.kick1(dt_mesh)
+        return self._read_records()
+
+    def kick1(self, dt_mesh: float):
+        """Both first half-kicks and the push of v_full."""
+        self.gas_mesh_kicks += 1 if dt_mesh != 0.0 else 0
+        self.sp.kick1_linked(self._kick_params(), self.P, dt_mesh)
+        self.gs.kick1(self._gkick_params(dt_mesh))
+        self._push(v_full=True)
+
+    def drift_to_next(self):
+        """Choose the next ti_current, drift both sides there, hand the gas
+        positions to the gas gparts, rebuild the tree. Returns (the space's
+        abi.DriftParams, the time drifted)."""
+        ti_old = self.ti_current
+        self.ti_current = int(self.result["ti_end_min"])
+        if not ti_old < self.ti_current <= MAX_NR_TIMESTEPS:
+            raise RuntimeError(f"time line exhausted or stalled at {ti_old} -> {self.ti_current}")
+        self.max_active_bin = get_max_active_bin(self.ti_current)
+        self._update_scalars()
+        dt = (self.ti_current - ti_old) * self.time_base
+        Dp = abi.DriftParams(dt, dt, dt, dt, self.min_u)
+        self.sp.drift(Dp, self.P)
+        info = self.sp.info()
+        if info["dx_max"] > self.max_rel_dx * min(info["cell_width"]):
+            self.sp.rebuild(self.P)
+            self.rebuilds += 1
+        self.gs.drift(dt, self.periodic, (self.box,) * 3)
+        self._push(x=True)
+        self._build()
+        return Dp, dt
+
+    def forces(self):
+        """Gravity on the gspace's stream and the hydro chain on the space's
+        (independent until the pull), then the pull."""
+        self.gravity()
+        self.chain = self.sp.hydro_step(self.P)
+        self.sp.pull_gravity()
+        return self.chain
+
+    def end_step(self) -> dict:
+        dt2, dt1 = self._mesh_kicks_here()
+        self.gas_mesh_kicks += (dt2 != 0.0) + (dt1 != 0.0)
+        K = self._kick_params()
+        self.sp.end_step_linked(K, self.T, K, self.P, dt2, dt1)
+        self.gs.end_step(self._gkick_params(dt2), self.GT, self._gkick_params(dt1))
+        self._push(v_full=True, time_bin=True)
+        return self._read_records()
+
+    def step(self) -> dict:
+        self.drift_to_next()
+        self.forces()
         return self.end_step()
 
     @property

@@ -59,6 +59,9 @@ HIP_SYMBOLS = [
     "swh_gspace_init_grav", "swh_gspace_end_force", "swh_gspace_kick1", "swh_gspace_kick2",
     "swh_gspace_timestep", "swh_gspace_end_step", "swh_gspace_step_result",
     "swh_gspace_step_times",
+    "swh_space_link_gspace", "swh_space_pull_gravity", "swh_space_push_gparts",
+    "swh_space_kick1_linked", "swh_space_kick2_linked", "swh_space_timestep_linked",
+    "swh_space_end_step_linked", "swh_space_link_times",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -198,6 +201,15 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
                                           P(abi.GKickParams)]),
         "swh_gspace_step_result": (C.c_int, [vp, P(abi.StepResult)]),
         "swh_gspace_step_times": (C.c_int, [vp, P(C.c_float)]),
+        "swh_space_link_gspace": (C.c_int, [vp, vp, P(i64)]),
+        "swh_space_pull_gravity": (C.c_int, [vp]),
+        "swh_space_push_gparts": (C.c_int, [vp, P(abi.PushParams)]),
+        "swh_space_kick1_linked": (C.c_int, [vp, P(abi.KickParams), P(abi.HydroParams), dp]),
+        "swh_space_kick2_linked": (C.c_int, [vp, P(abi.KickParams), P(abi.HydroParams), dp]),
+        "swh_space_timestep_linked": (C.c_int, [vp, P(abi.TimestepParams), P(abi.HydroParams)]),
+        "swh_space_end_step_linked": (C.c_int, [vp, P(abi.KickParams), P(abi.TimestepParams),
+                                                P(abi.KickParams), P(abi.HydroParams), dp, dp]),
+        "swh_space_link_times": (C.c_int, [vp, P(C.c_float)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -509,6 +521,60 @@ class HydroSpace:
     def unpack_halo(self, idx_ptr: int, n: int, in_ptr: int, fields: int = 31):
         _check(self._lib.swh_space_unpack_halo(self.handle, C.c_void_p(idx_ptr), n,
                                                C.c_void_p(in_ptr), fields), "unpack_halo", self._lib)
+
+    # ---- gas <-> gpart link (swh_couple.hip) -------------------------------
+    def link(self, gspace: "GravSpace") -> int:
+        """Link the parts to the gas gparts of `gspace` (id_or_neg_offset =
+        minus the part's index); checked on the device. Returns the number of
+        pairs. Needs the parts, the xparts and the gparts uploaded."""
+        n = C.c_int64(0)
+        _check(self._lib.swh_space_link_gspace(self.handle, gspace.handle, C.byref(n)), "link",
+               self._lib)
+        return n.value
+
+    def unlink(self):
+        _check(self._lib.swh_space_link_gspace(self.handle, None, None), "unlink", self._lib)
+
+    def pull_gravity(self):
+        """The linked gparts' a_grav and a_grav_mesh into the space (after the
+        gspace's end_force); holds until the next rebuild."""
+        _check(self._lib.swh_space_pull_gravity(self.handle), "pull_gravity", self._lib)
+
+    def push_gparts(self, x: bool = False, v_full: bool = False, time_bin: bool = False,
+                    periodic: bool = False, dim=(1.0, 1.0, 1.0)):
+        """The parts' position, xp->v_full and time_bin into their gparts' records."""
+        what = ((abi.PUSH_X if x else 0) | (abi.PUSH_V_FULL if v_full else 0) |
+                (abi.PUSH_TIME_BIN if time_bin else 0))
+        Q = abi.PushParams(what, periodic, dim)
+        _check(self._lib.swh_space_push_gparts(self.handle, C.byref(Q)), "push_gparts", self._lib)
+
+    def kick1_linked(self, K: abi.KickParams, P: abi.HydroParams, dt_mesh: float = 0.0):
+        """kick1 with the linked gparts' tree and mesh accelerations; sets the
+        drift's xp->a_grav."""
+        _check(self._lib.swh_space_kick1_linked(self.handle, C.byref(K), C.byref(P), dt_mesh),
+               "kick1_linked", self._lib)
+
+    def kick2_linked(self, K: abi.KickParams, P: abi.HydroParams, dt_mesh: float = 0.0):
+        _check(self._lib.swh_space_kick2_linked(self.handle, C.byref(K), C.byref(P), dt_mesh),
+               "kick2_linked", self._lib)
+
+    def timestep_linked(self, T: abi.TimestepParams, P: abi.HydroParams):
+        _check(self._lib.swh_space_timestep_linked(self.handle, C.byref(T), C.byref(P)),
+               "timestep_linked", self._lib)
+
+    def end_step_linked(self, K2: abi.KickParams, T: abi.TimestepParams, K1: abi.KickParams,
+                        P: abi.HydroParams, dt_mesh2: float = 0.0, dt_mesh1: float = 0.0):
+        """kick2, timestep and kick1 of a linked space in one launch."""
+        _check(self._lib.swh_space_end_step_linked(self.handle, C.byref(K2), C.byref(T),
+                                                   C.byref(K1), C.byref(P), dt_mesh2, dt_mesh1),
+               "end_step_linked", self._lib)
+
+    def link_ms(self) -> dict:
+        """HIP-event times (ms) of the last pull, push and linked kick /
+        timestep launch (-1: not run)."""
+        ms = (C.c_float * 3)()
+        _check(self._lib.swh_space_link_times(self.handle, ms), "link_times", self._lib)
+        return dict(zip(("pull", "push", "end_step"), map(float, ms)))
 
     def hydro_step(self, P):
         """The full SPHENIX hydro chain of one step:
