@@ -7,7 +7,8 @@
 //   interact() : the non-symmetric iact (hydro_iact.h:130, 276, 488)
 //   store()    : accumulate into the particle's fields (SWIFT "+=" semantics)
 //   kPay / load_j() / interact_staged(): the j-side record a list walk loads
-//                (kPay float4s + one int) and the iact on it
+//                (kPay float4s + one int) and the iact on it; load_j<true>
+//                gathers with 32-bit byte offsets (gather_at)
 //
 // The list walks (swh_list.h) evaluate these states entry by entry; the
 // wave-per-particle search of list overflow and ghost reruns walks the grid
@@ -34,6 +35,22 @@ struct JRec {
   float4 p[N];
   int meta;
 };
+
+// A gather of the force list walk. O32: the array's (wave-uniform)
+// base plus a 32-bit byte offset, one shift per stride (records of equal
+// stride share it) where base[j] costs a sign extension, a 64-bit shift and a
+// 64-bit add per gather; it needs n * sizeof(V) < 2^32 for every array
+// (walk_off32, swh_hydro.hip). Otherwise plain indexing.
+template <bool O32, typename V>
+__device__ __forceinline__ V gather_at(const V* base, int j) {
+  if constexpr (O32) {
+    static_assert((sizeof(V) & (sizeof(V) - 1)) == 0, "the offset is one shift");
+    return *reinterpret_cast<const V*>(reinterpret_cast<const char*>(base) +
+                                       (unsigned int)j * (unsigned int)sizeof(V));
+  } else {
+    return base[j];
+  }
+}
 
 // fp64 (the batch path): the sums of iact_nonsym_density_raw, finalized at
 // the store; fp32 (SWH_PRECISION_F32): the reference's own arithmetic.
@@ -75,6 +92,7 @@ struct LoopState<LOOP_DENSITY, T> {
     n++;
   }
   static constexpr int kPay = 1;
+  template <bool O32 = false>  // (the density walk gathers by plain indexing)
   __device__ static __forceinline__ JRec<1> load_j(const SoA& a, int j) {
     JRec<1> r;
     r.p[0] = a.vm[j];
@@ -143,6 +161,7 @@ struct LoopState<LOOP_GRADIENT, T> {
     n++;
   }
   static constexpr int kPay = 2;
+  template <bool O32 = false>  // (the gradient walk gathers by plain indexing)
   __device__ static __forceinline__ JRec<2> load_j(const SoA& a, int j) {
     const float4 t = a.th[j];
     JRec<2> r;
@@ -215,12 +234,13 @@ struct LoopState<LOOP_FORCE, T> {
     n++;
   }
   static constexpr int kPay = 3;
+  template <bool O32 = false>
   __device__ static __forceinline__ JRec<3> load_j(const SoA& a, int j) {
     JRec<3> r;
-    r.p[0] = a.vm[j];
-    r.p[1] = a.th[j];
-    r.p[2] = a.fc[j];
-    r.meta = a.tb[j];
+    r.p[0] = gather_at<O32>(a.vm, j);
+    r.p[1] = gather_at<O32>(a.th, j);
+    r.p[2] = gather_at<O32>(a.fc, j);
+    r.meta = gather_at<O32>(a.tb, j);
     return r;
   }
   __device__ __forceinline__ void interact_staged(const float4* p, int tbj, const double4& pj,

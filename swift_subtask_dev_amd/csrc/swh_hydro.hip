@@ -194,7 +194,9 @@ void list_build_kernel(GridDev g, SoA a, ListDev ld,
 #ifndef SWH_WALK_WPE_DENS
 #define SWH_WALK_WPE_DENS 4
 #endif
-template <int LOOP, typename T>
+// O32: the force walk gathers by 32-bit byte offsets (gather_at; the launch
+// checks the range).
+template <int LOOP, typename T, bool O32>
 __global__ __launch_bounds__(kWalkBlock)
 #if SWH_WALK_WPE > 0
 __attribute__((amdgpu_waves_per_eu(SWH_WALK_WPE)))
@@ -204,7 +206,8 @@ void walk_kernel(GridDev g, SoA a, ListDev ld, int i0, int n,
                                                    const unsigned int* __restrict__ hmax_bits,
                                                    unsigned long long* counter,
                                                    int* __restrict__ ncount) {
-  list_walk<LOOP, T, kWalkLpi>(g, a, ld, i0, n, max_active_bin, a2H, hmax_bits, counter, ncount);
+  list_walk<LOOP, T, kWalkLpi, O32>(g, a, ld, i0, n, max_active_bin, a2H, hmax_bits, counter,
+                                     ncount);
 }
 
 // The density walk held to 4 waves/SIMD (its four entries in flight per lane
@@ -931,6 +934,13 @@ static swh_status check_kept_lists(swh_space* s, const swh_hydro_params* P, bool
   return build_lists(s, P, count, s->tuning.list_skin, keep_stale_slot(s));
 }
 
+// May the force walk gather by 32-bit byte offsets? The widest array
+// (pos, 32 B per particle) must end below 2^32 bytes; a larger space walks
+// with plain 64-bit indexing.
+static bool walk_off32(const swh_space* s) {
+  return (unsigned long long)s->n * sizeof(double4) < (1ull << 32);
+}
+
 template <int LOOP, typename T>
 static void launch_typed(swh_space* s, const GridDev& gd, const SegList* subset, int nitems,
                          int max_active_bin, T a2H, unsigned long long* ctr, int* ncount,
@@ -958,8 +968,12 @@ static void launch_typed(swh_space* s, const GridDev& gd, const SegList* subset,
     hipLaunchKernelGGL((density_walk_kernel<T>), dim3((nitems + wppb - 1) / wppb),
                        dim3(kWalkBlock), 0, s->stream, gd, soa_of(s), ld, 0, nitems,
                        max_active_bin, a2H, hmax_slot(s), ctr, ncount);
+  else if (LOOP == LOOP_FORCE && walk_off32(s))
+    hipLaunchKernelGGL((walk_kernel<LOOP, T, LOOP == LOOP_FORCE>), dim3((nitems + wppb - 1) / wppb),
+                       dim3(kWalkBlock), 0, s->stream, gd, soa_of(s), ld, 0, nitems,
+                       max_active_bin, a2H, hmax_slot(s), ctr, ncount);
   else
-    hipLaunchKernelGGL((walk_kernel<LOOP, T>), dim3((nitems + wppb - 1) / wppb),
+    hipLaunchKernelGGL((walk_kernel<LOOP, T, false>), dim3((nitems + wppb - 1) / wppb),
                        dim3(kWalkBlock), 0, s->stream, gd, soa_of(s), ld, 0, nitems,
                        max_active_bin, a2H, hmax_slot(s), ctr, ncount);
   hipLaunchKernelGGL((overflow_kernel<LOOP, T>), dim3(64), dim3(block), 0, s->stream, gd,

@@ -17,11 +17,12 @@ for r in rows:
     by[r["Kernel_Name"].split("(")[0]].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-3)
 dens = ["swh::group_prep_kernel", "swh::list_build_kernel", "void swh::density_walk_kernel<double>",
         "void swh::overflow_kernel<0, double>"]
-force = ["void swh::walk_kernel<2, double>", "void swh::overflow_kernel<2, double>"]
+# (the walk's third template argument, its gather addressing, varies with the space's size)
+force = ["void swh::walk_kernel<2, double", "void swh::overflow_kernel<2, double>"]
 out = {"kernels_us": {}, "line": {"density_ms": d["kernels"]["density_ms"],
                                   "force_ms": d["kernels"]["force_ms"]}}
 for k in dens + force:
-    v = by.get(k, [])[-steps:]
+    v = [x for name in by if name.startswith(k) for x in by[name]][-steps:]
     out["kernels_us"][k] = statistics.mean(v) if v else None
 out["trace_density_ms"] = sum(out["kernels_us"][k] or 0 for k in dens) * 1e-3
 out["trace_force_ms"] = sum(out["kernels_us"][k] or 0 for k in force) * 1e-3
