@@ -457,6 +457,97 @@ SWH_API swh_status swh_space_download_xparts(swh_space *s, void *xparts,
  * step, and re-uploading whole xparts would overwrite the kicked v_full. */
 SWH_API swh_status swh_space_upload_a_grav(swh_space *s, const float *a_grav, int on_device);
 
+/* ------------------------------------------------------------------ */
+/* Time-step limiter (swift --limiter) for the gas of a swh_space: the */
+/* two tasks between runner_do_timestep and runner_do_kick1.           */
+/*   swh_space_limiter_loop   the limiter neighbour loop               */
+/*                      (runner_doiact_functions_limiter.h,            */
+/*                      runner_iact_nonsym_limiter,                    */
+/*                      timestep_limiter_iact.h:105-115): every        */
+/*                      starting particle i (owned, not inhibited, new */
+/*                      time_bin <= max_active_bin) visits the owned,  */
+/*                      not inhibited j != i with r < kernel_gamma h_i; */
+/*                      where time_bin_j > time_bin_i + 2,             */
+/*                      wakeup_j = max(wakeup_j, -time_bin_i). j may   */
+/*                      itself be active. Foreign halo copies are      */
+/*                      never written (cross-rank wake-ups are the     */
+/*                      caller's).                                     */
+/*   swh_space_limiter_apply  runner_do_limiter                        */
+/*                      (runner_time_integration.c:1386-1453) with     */
+/*                      timestep_limit_part (timestep_limiter.h:       */
+/*                      64-217) on every owned, not inhibited particle */
+/*                      whose wake-up is set: new bin -wakeup + 2; an  */
+/*                      inactive one has its kick1 undone and is       */
+/*                      kicked to the start of its new step, and       */
+/*                      given that step's kick1 if kick1 will not      */
+/*                      start it (new bin > max_active_bin). Wake-ups  */
+/*                      are reset to not-awake (-SWH_NUM_TIME_BINS),   */
+/*                      ti_end_new / ti_beg_new merged into the record */
+/*                      swh_space_step_result returns.                 */
+/*   swh_space_end_step_limited  kick2 + timestep, the loop on the     */
+/*                      step's pair lists (still valid: the starting   */
+/*                      particles are the active ones), apply, kick1.  */
+/*                      The same bits as swh_space_kick2, _timestep,   */
+/*                      _limiter_loop, _limiter_apply, _kick1 in turn, */
+/*                      where the loop finds no lists (the time step   */
+/*                      dropped them) and builds them.                 */
+/* The wake-up of every particle lives on the device from the upload   */
+/* of the parts on (not awake) and follows swh_space_rebuild's         */
+/* re-sort; it is not part of swh_part_layout. All calls only enqueue. */
+/* A space linked to a gspace gets SWH_ERR_STATE: the coupled step's   */
+/* limiter must also hand the new bin to the gas gpart.                */
+/* runner_do_sync (limiter_data.to_be_synchronized) is not built.      */
+/* ------------------------------------------------------------------ */
+typedef struct swh_limiter_params {
+  int64_t ti_current;     /* e->ti_current */
+  double time_base;       /* e->time_base  */
+  int32_t max_active_bin; /* e->max_active_bin (== the swh_hydro_params') */
+  float min_u;            /* as swh_kick_params.min_u */
+  /* Kick intervals per time bin b (SWH_NUM_TIME_BINS + 1 entries each,
+   * nullable in pairs per kind). NULL: non-cosmological, every interval is an
+   * integer tick difference times time_base. With cosmology, for
+   * ti_beg(b) = get_integer_time_begin(ti_current + 1, b) and the integrand of
+   * kick_get_hydro_kick_dt / _grav_ / _therm_ (src/kick.h:46-135):
+   *   first_half[b]  = integral over [ti_beg(b), ti_beg(b) + ti_step(b) / 2]
+   *   since_begin[b] = integral over [ti_beg(b), ti_current]
+   * The un-kick is -first_half[old], the kick to the start of the new step
+   * since_begin[old] - since_begin[new], the missing kick1 first_half[new]. */
+  const double *first_half_hydro;
+  const double *first_half_grav;
+  const double *first_half_therm;
+  const double *since_begin_hydro;
+  const double *since_begin_grav;
+  const double *since_begin_therm;
+} swh_limiter_params;
+
+/* Counts of the last swh_space_limiter_apply / swh_space_end_step_limited. */
+typedef struct swh_limiter_result {
+  int64_t n_woken_active;   /* active particles given a shorter new step */
+  int64_t n_woken_inactive; /* inactive particles woken (re-kicked) */
+  int32_t min_new_bin;      /* smallest bin handed out; SWH_NUM_TIME_BINS + 1: none */
+  int32_t reserved;
+} swh_limiter_result;
+
+/* P: max_active_bin (the starting set) and the loops' other scalars. Builds
+ * the pair lists if the space has none for P->max_active_bin. */
+SWH_API swh_status swh_space_limiter_loop(swh_space *s, const swh_hydro_params *P);
+/* The wake-up of every particle (int8, caller order; not awake:
+ * -SWH_NUM_TIME_BINS); waits for the stream. For tests and schedulers. */
+SWH_API swh_status swh_space_download_wakeup(swh_space *s, int8_t *out, int on_device);
+/* SWH_ERR_STATE before a swh_space_timestep (there is no record to merge
+ * into) or swh_space_upload_xparts. Drops the pair lists: a woken particle
+ * may have entered the active bins. */
+SWH_API swh_status swh_space_limiter_apply(swh_space *s, const swh_limiter_params *L,
+                                           const swh_hydro_params *P);
+SWH_API swh_status swh_space_end_step_limited(swh_space *s, const swh_kick_params *K2,
+                                              const swh_timestep_params *T,
+                                              const swh_kick_params *K1,
+                                              const swh_limiter_params *L,
+                                              const swh_hydro_params *P);
+/* Waits for the last apply. SWH_ERR_STATE when none was queued since the
+ * upload of the parts. */
+SWH_API swh_status swh_space_limiter_result(swh_space *s, swh_limiter_result *out);
+
 /* Wait for all queued work on the space's stream. */
 SWH_API swh_status swh_space_sync(swh_space *s);
 /* Without waiting: SWH_OK when all queued work on the space's stream has

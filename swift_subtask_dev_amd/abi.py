@@ -218,6 +218,38 @@ class StepResult(C.Structure):
                 ("vfull_max", C.c_float), ("reserved", C.c_int32)]
 
 
+TIME_BIN_NOT_AWAKE = -NUM_TIME_BINS  # src/timeline.h time_bin_not_awake
+
+
+class LimiterParams(C.Structure):
+    """swh_limiter_params: the apply stage of the time-step limiter."""
+
+    _KINDS = ("hydro", "grav", "therm")
+    _fields_ = ([("ti_current", C.c_int64), ("time_base", C.c_double),
+                 ("max_active_bin", C.c_int32), ("min_u", C.c_float)] +
+                [(f"first_half_{k}", C.POINTER(C.c_double)) for k in _KINDS] +
+                [(f"since_begin_{k}", C.POINTER(C.c_double)) for k in _KINDS])
+
+    def set_tables(self, first_half=None, since_begin=None) -> None:
+        """Per-time-bin kick intervals (cosmological runs,
+        cosmo.limiter_tables): two dicts of the hydro / grav / therm tables;
+        None: the non-cosmological integer tick differences times time_base.
+        The arrays are kept alive by this object."""
+        self._keep = []
+        for prefix, tabs in (("first_half", first_half), ("since_begin", since_begin)):
+            for k in self._KINDS:
+                arr, ptr = _bin_table(None if tabs is None else tabs.get(k))
+                self._keep.append(arr)
+                setattr(self, f"{prefix}_{k}", ptr)
+
+
+class LimiterResult(C.Structure):
+    """swh_limiter_result."""
+
+    _fields_ = [("n_woken_active", C.c_int64), ("n_woken_inactive", C.c_int64),
+                ("min_new_bin", C.c_int32), ("reserved", C.c_int32)]
+
+
 class DriftParams(C.Structure):
     """swh_drift_params (== the oracle's oracle_drift_params)."""
 

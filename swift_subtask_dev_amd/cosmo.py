@@ -167,6 +167,29 @@ def kick_tables(cosmo: Cosmology, ti_current: int, kick: int) -> dict:
     return out
 
 
+def limiter_tables(cosmo: Cosmology, ti_current: int) -> tuple:
+    """swh_limiter_params' per-bin kick intervals at ti_current with cosmology
+    (timestep_limit_part, src/timestep_limiter.h:137-204), from the integrals
+    of kick_tables. For every bin b whose step [ti_beg, ti_beg + ti_step) holds
+    ti_current (ti_beg = ti_current where a step of the bin starts there):
+    first_half[b] over [ti_beg, ti_beg + ti_step / 2], since_begin[b] over
+    [ti_beg, ti_current]. Returns (first_half, since_begin), each a dict of
+    the hydro / grav / therm tables."""
+    first = {k: np.zeros(NUM_TIME_BINS + 1) for k in ("hydro", "grav", "therm")}
+    since = {k: np.zeros(NUM_TIME_BINS + 1) for k in ("hydro", "grav", "therm")}
+    powers = {"grav": 1.0, "hydro": 3.0 * (HYDRO_GAMMA - 1.0), "therm": 2.0}
+    for b in range(1, NUM_TIME_BINS + 1):
+        step = get_integer_timestep(b)
+        beg = get_integer_time_begin(ti_current + 1, b)
+        if beg + step > MAX_NR_TIMESTEPS:
+            continue  # no such step on the time line
+        for k, p in powers.items():
+            first[k][b] = _kick_integral(cosmo, beg, beg + step // 2, p)
+            if beg < ti_current:
+                since[k][b] = _kick_integral(cosmo, beg, ti_current, p)
+    return first, since
+
+
 def cosmological_params(cosmo: Cosmology, ti_current: int, dim=(1.0, 1.0, 1.0),
                         periodic=True, **kw) -> abi.HydroParams:
     """swh_hydro_params of a cosmological step: a, H, a^-2 and the gamma = 5/3

@@ -9,6 +9,8 @@
 //   kPay / load_j() / interact_staged(): the j-side record a list walk loads
 //                (kPay float4s + one int) and the iact on it; load_j<true>
 //                gathers with 32-bit byte offsets (gather_at)
+// A fourth state, the time-step limiter's, gathers the same way and scatters
+// wake-ups instead of accumulating (r < H_i).
 //
 // The list walks (swh_list.h) evaluate these states entry by entry; the
 // wave-per-particle search of list overflow and ghost reruns walks the grid
@@ -17,10 +19,11 @@
 
 #include "swh_physics.h"
 #include "swh_space.h"
+#include "swh_timeline.h"
 
 namespace swh {
 
-enum { LOOP_DENSITY = 0, LOOP_GRADIENT = 1, LOOP_FORCE = 2 };
+enum { LOOP_DENSITY = 0, LOOP_GRADIENT = 1, LOOP_FORCE = 2, LOOP_LIMITER = 3 };
 
 __device__ __forceinline__ double wrap_nearest(double d, double box) {
   return d > 0.5 * box ? d - box : (d < -0.5 * box ? d + box : d);
@@ -264,6 +267,69 @@ struct LoopState<LOOP_FORCE, T> {
     a.hdt[i] = (float)((T)a.hdt[i] + A.h_dt);
     a.mintb[i] = (int8_t)A.min_ngb_time_bin;
   }
+};
+
+// The time-step limiter's neighbour loop (runner_doiact_functions_limiter.h,
+// runner_iact_nonsym_limiter): a gather from every starting i over r < H_i
+// like density and gradient, whose "interaction" is a scatter: a neighbour
+// more than time_bin_neighbour_max_delta_bin bins above i gets
+// wakeup_j = max(wakeup_j, -tb_i), an integer max on j's 32-bit wake-up word
+// so the result does not depend on the order of the pairs. The words come in
+// through load_i's last argument, the loop's auxiliary device array (the force
+// loop's is max h): the SoA and the kernels' signatures stay as they are. The
+// entry's payload is the neighbour's int8 bin; ownership (foreign halo copies
+// are never written) is looked up only for the few pairs that wake.
+template <typename T>
+struct LoopState<LOOP_LIMITER, T> {
+  int self, n, tbi, n_owned;
+  double reach;
+  T hig2;
+  int* wake;
+  const int* perm;
+  __device__ __forceinline__ void load_i(const SoA& a, int i, T, const unsigned int* wake_words) {
+    const double4 p = a.pos[i];
+    const T hi = (T)p.w;
+    self = i;
+    n = 0;
+    tbi = a.tb[i];
+    n_owned = a.n_owned;
+    hig2 = hi * hi * (T)kGamma2;
+    reach = p.w * (double)kGamma;
+    // (writable device memory of the space, typed as the other loops' read-only array)
+    wake = reinterpret_cast<int*>(const_cast<unsigned int*>(wake_words));
+    perm = a.perm;
+  }
+  __device__ __forceinline__ bool accept(int j, const double4&, T r2) const {
+    return (r2 < hig2) & (j != self);
+  }
+  __device__ __forceinline__ void wake_up(int j, int tbj) {
+    n++;
+    // time_bin_neighbour_max_delta_bin; -tbi below is never under
+    // time_bin_not_awake, the words' initial value
+    if (tbj <= tbi + kMaxDeltaBin || tbj == kTimeBinInhibited) return;
+    if (perm[j] >= n_owned) return;
+    // (an atomic only where it changes the word: most of a sleeper's
+    // neighbours carry the same bin)
+    if (__hip_atomic_load(&wake[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < -tbi)
+      atomicMax(&wake[j], -tbi);
+  }
+  __device__ __forceinline__ void interact(const SoA& a, int j, const double4&, T, T, T, T) {
+    wake_up(j, a.tb[j]);
+  }
+  static constexpr int kPay = 1;  // walked four entries at a time, as density
+  template <bool O32 = false>
+  __device__ static __forceinline__ JRec<1> load_j(const SoA& a, int j) {
+    JRec<1> r;
+    // the record carries the entry's index (the scatter's target), no field
+    r.p[0] = make_float4(__int_as_float(j), 0.f, 0.f, 0.f);
+    r.meta = a.tb[j];
+    return r;
+  }
+  __device__ __forceinline__ void interact_staged(const float4* p, int tbj, const double4&, T, T,
+                                                  T, T) {
+    wake_up(__float_as_int(p[0].x), tbj);
+  }
+  __device__ __forceinline__ void store(SoA&, int) const {}
 };
 
 // Grid-cell range of one particle: cells overlapping [x - R, x + R] per

@@ -9,7 +9,8 @@
 // so the sums are deterministic and need no atomics. The loops walk the
 // step's pair lists (swh_list.h); particles the lists do not cover (list
 // overflow, ghost reruns whose h outgrew the list reach) take a
-// wave-per-particle search of the grid cells around them.
+// wave-per-particle search of the grid cells around them. The time-step
+// limiter's wake-up loop (LOOP_LIMITER, swh_gather.h) walks the same lists.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -941,6 +942,13 @@ static bool walk_off32(const swh_space* s) {
   return (unsigned long long)s->n * sizeof(double4) < (1ull << 32);
 }
 
+// The auxiliary device array a loop's states get (load_i's last argument): max
+// h over the set (float bits), or the limiter's wake-up words.
+template <int LOOP>
+static const unsigned int* loop_aux(swh_space* s) {
+  return LOOP == LOOP_LIMITER ? s->wake_s.as<const unsigned int>() : hmax_slot(s);
+}
+
 template <int LOOP, typename T>
 static void launch_typed(swh_space* s, const GridDev& gd, const SegList* subset, int nitems,
                          int max_active_bin, T a2H, unsigned long long* ctr, int* ncount,
@@ -975,9 +983,9 @@ static void launch_typed(swh_space* s, const GridDev& gd, const SegList* subset,
   else
     hipLaunchKernelGGL((walk_kernel<LOOP, T, false>), dim3((nitems + wppb - 1) / wppb),
                        dim3(kWalkBlock), 0, s->stream, gd, soa_of(s), ld, 0, nitems,
-                       max_active_bin, a2H, hmax_slot(s), ctr, ncount);
+                       max_active_bin, a2H, loop_aux<LOOP>(s), ctr, ncount);
   hipLaunchKernelGGL((overflow_kernel<LOOP, T>), dim3(64), dim3(block), 0, s->stream, gd,
-                     soa_of(s), ld, ld.ovf, ld.ovf_n, max_active_bin, a2H, hmax_slot(s), ctr,
+                     soa_of(s), ld, ld.ovf, ld.ovf_n, max_active_bin, a2H, loop_aux<LOOP>(s), ctr,
                      ncount);
 }
 
@@ -1044,12 +1052,12 @@ static swh_status launch_loop(swh_space* s, const swh_hydro_params* P, const Seg
     const int* q = s->grown_search.as<const int>();
     if (f64)
       hipLaunchKernelGGL((overflow_kernel<LOOP, double>), dim3(256), dim3(256), 0, s->stream,
-                         gd, soa_of(s), ld, q, qn, P->max_active_bin, a2H, hmax_slot(s), ctr,
+                         gd, soa_of(s), ld, q, qn, P->max_active_bin, a2H, loop_aux<LOOP>(s), ctr,
                          ncount);
     else
       hipLaunchKernelGGL((overflow_kernel<LOOP, float>), dim3(256), dim3(256), 0, s->stream,
                          gd, soa_of(s), ld, q, qn, P->max_active_bin, (float)a2H,
-                         hmax_slot(s), ctr, ncount);
+                         loop_aux<LOOP>(s), ctr, ncount);
     hipLaunchKernelGGL(grown_clear_kernel, dim3(64), dim3(256), 0, s->stream, q, qn, mark);
   }
   SWH_HIP(hipGetLastError());
@@ -1091,6 +1099,23 @@ static swh_status run_loop(swh_space* s, const swh_hydro_params* P, int64_t* n_o
     }
   }
   return SWH_OK;
+}
+
+// The limiter's neighbour loop (runner_doiact_functions_limiter.h) as a
+// fourth loop kind over the step's pair lists: the force lists hold
+// r < max(R_i, R_j) for exactly the active i, positions and h have not changed
+// since the force loop, and after the time step the starting particles are
+// the active ones, so the walk takes the r < H_i subset of the same entries,
+// with the same two side paths (list overflow, ghost-grown H). Called with
+// no valid lists (after swh_space_timestep dropped them) it builds them for
+// the starting set first.
+swh_status space_limiter_walk(swh_space* s, const swh_hydro_params* P) {
+  SWH_TRY(check_built(s));
+  if (!s->wake_sorted) {
+    set_error("the limiter walk needs the wake-up words in sorted order");
+    return SWH_ERR_STATE;
+  }
+  return launch_loop<LOOP_LIMITER>(s, P, nullptr, (int)s->n, false);
 }
 
 }  // namespace swh

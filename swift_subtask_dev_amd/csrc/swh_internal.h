@@ -198,6 +198,17 @@ struct swh_space {
   hipEvent_t step_event = nullptr;  // behind the last record copy
   bool step_pending = false;  // a record copy is queued and not yet read (vfull_max)
   bool step_has_ts = false;   // the record holds a timestep's fields
+  // time-step limiter (swh_limiter.hip): the wake-up word of every particle
+  // (i32, the reference's int8 limiter_data.wakeup widened for the integer
+  // atomic max of the neighbour loop), authoritative in sorted order
+  // (wake_sorted) or, across a re-sort, in caller order (wake_caller);
+  // neither: every particle is not awake. lim_rec: u32[4] counts of the last
+  // apply, read back into lim_host behind lim_event.
+  swh::DevBuf wake_s, wake_c, lim_rec;
+  bool wake_sorted = false, wake_caller = false;
+  swh::HostBuf lim_host;
+  hipEvent_t lim_event = nullptr;
+  bool lim_has = false;
   // gas <-> gpart link (swh_couple.hip): the gspace whose gas gparts name this
   // space's parts, their a_grav and a_grav_mesh in sorted order (float4, filled
   // by swh_space_pull_gravity, void after a rebuild), the check's scratch

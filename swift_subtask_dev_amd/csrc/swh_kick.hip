@@ -52,8 +52,7 @@ struct TimestepDev {
   int64_t ti_current;
 };
 
-// record slots (u64 each, all reduced by atomicMax / atomicAdd from zero)
-enum { REC_END_MIN = 0, REC_END_MAX, REC_BEG_MAX, REC_UPDATED, REC_BELOW, REC_VMAX, REC_SLOTS = 8 };
+// (the record slots REC_*: swh_space.h)
 
 // the row of the per-bin half-step tables for time bin `bin`
 __device__ __forceinline__ int kick_bin(int bin) {
@@ -377,7 +376,7 @@ template <bool K2, bool TS, bool K1, bool LK = false>
 static swh_status launch_step(swh_space* s, const swh_kick_params* k2,
                               const swh_timestep_params* T, const swh_kick_params* k1,
                               const swh_hydro_params* P, const char* what, double dt_mesh2 = 0.,
-                              double dt_mesh1 = 0.) {
+                              double dt_mesh1 = 0., bool keep_lists = false) {
   if (!s || !P || (K2 && !k2) || (TS && !T) || (K1 && !k1)) return SWH_ERR_ARG;
   if (LK && !s->link) {
     set_error("swh_space_link_gspace must precede %s", what);
@@ -431,11 +430,26 @@ static swh_status launch_step(swh_space* s, const swh_kick_params* k2,
     // host-only note next to the record: the dt_min of step_result's message
     static_cast<double*>(s->step_host.ptr)[REC_SLOTS] = T->dt_min;
     // the pair lists hold the active particles of the bins they were built
-    // with (list_mab only remembers max_active_bin): a bin may have changed
-    s->list_valid = false;
-    s->list_check = false;
+    // with (list_mab only remembers max_active_bin): a bin may have changed.
+    // keep_lists: the limited end of step walks them once more first -- the
+    // starting particles are the active ones -- and drops them itself
+    if (!keep_lists) {
+      s->list_valid = false;
+      s->list_check = false;
+    }
   }
   return SWH_OK;
+}
+
+swh_status space_kick2_timestep_keep_lists(swh_space* s, const swh_kick_params* K2,
+                                           const swh_timestep_params* T,
+                                           const swh_hydro_params* P, const char* what) {
+  return launch_step<true, true, false>(s, K2, T, nullptr, P, what, 0., 0., true);
+}
+
+swh_status space_kick1(swh_space* s, const swh_kick_params* K1, const swh_hydro_params* P,
+                       const char* what) {
+  return launch_step<false, false, true>(s, nullptr, nullptr, K1, P, what);
 }
 
 // The latest record's max |v_full| bounds the next drift's displacement.

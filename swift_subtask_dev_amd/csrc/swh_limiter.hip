@@ -1,0 +1,385 @@
+// swh_limiter.hip — the time-step limiter of the batch path, the two tasks
+// SWIFT runs between runner_do_timestep and runner_do_kick1 under --limiter:
+//   the limiter neighbour loop  (src/runner_doiact_functions_limiter.h with
+//                               runner_iact_nonsym_limiter,
+//                               timestep_limiter_iact.h:105-115)
+//   runner_do_limiter           (src/runner_time_integration.c:1386-1453) with
+//                               timestep_limit_part (timestep_limiter.h:64-217)
+// for the gas particles of a swh_space. The loop is a fourth kind of list walk
+// (swh_hydro.hip space_limiter_walk, the state in swh_gather.h); this file
+// holds the wake-up words, the per-particle apply stage -- the arithmetic is
+// swh_limiter.h's, shared with a plain host program -- and the C entries,
+// among them the fused end of step that walks the pair lists before the time
+// step's new bins make them void.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "swh_internal.h"
+#include "swh_limiter.h"
+#include "swh_physics.h"
+#include "swh_space.h"
+#include "swh_wave.h"
+
+#pragma clang fp contract(off)
+
+namespace swh {
+
+namespace {
+
+// lim_rec slots (u32): woken active / inactive particles, 127 - min new bin
+enum { LIM_N_ACTIVE = 0, LIM_N_INACTIVE, LIM_MIN_BIN_C, LIM_SLOTS = 4 };
+
+__global__ void wake_fill_kernel(int* __restrict__ wake, int64_t n) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < n) wake[s] = kTimeBinNotAwake;
+}
+
+// caller order -> sorted order, and back (around a re-sort)
+__global__ void wake_sort_kernel(const int* __restrict__ perm, const int* __restrict__ wake_c,
+                                 int64_t n, int* __restrict__ wake_s) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < n) wake_s[s] = wake_c[perm[s]];
+}
+__global__ void wake_unsort_kernel(const int* __restrict__ perm, const int* __restrict__ wake_s,
+                                   int64_t n, int* __restrict__ wake_c) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < n) wake_c[perm[s]] = wake_s[s];
+}
+
+// The words narrowed to the reference's int8, caller order. perm: the words
+// are in sorted order; null: already in caller order; wake null: not awake.
+__global__ void wake_pack_kernel(const int* __restrict__ perm, const int* __restrict__ wake,
+                                 int64_t n, int8_t* __restrict__ out) {
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  out[perm ? perm[s] : s] = (int8_t)(wake ? wake[s] : kTimeBinNotAwake);
+}
+
+__device__ __forceinline__ long long wave_max_ll(long long v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const long long w = __shfl_xor(v, o);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ unsigned int wave_sum_u(unsigned int v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ unsigned int wave_max_u(unsigned int v) {
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned int)__shfl_xor(v, o));
+  return v;
+}
+// (an atomic only where it changes the word: the blocks' maxima mostly agree)
+__device__ __forceinline__ void atomic_max_u64_if(unsigned long long* p, unsigned long long v) {
+  if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
+}
+
+// runner_do_limiter over the owned, not inhibited particles whose wake-up word
+// is set: timestep_limit_part on the sorted SoA and xparts, the word reset,
+// ti_end_new / ti_beg_new merged into the step record (min into ti_end_min --
+// kept as max_nr_timesteps - ti_end -- max into ti_end_max and ti_beg_max,
+// max |v_full| of the re-kicked particles into the drift's bound).
+__global__ __launch_bounds__(256) void limiter_apply_kernel(
+    SoA a, float4* __restrict__ vfull, const float4* __restrict__ agrav,
+    const int8_t* __restrict__ hasg, int* __restrict__ wake, int64_t n, LimiterKicks K,
+    unsigned long long* __restrict__ rec, unsigned int* __restrict__ lim) {
+  __shared__ long long sm_t[3][4];
+  __shared__ unsigned int sm_c[3][4];
+  __shared__ float sm_v[4];
+  long long end_min_c = 0, end_max = 0, beg_max = 0;
+  unsigned int n_act = 0, n_inact = 0, min_bin_c = 0;
+  float vmax = 0.f;
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
+       s += (int64_t)gridDim.x * blockDim.x) {
+    const int w = wake[s];
+    if (w == kTimeBinNotAwake) continue;
+    wake[s] = kTimeBinNotAwake;
+    const int bin = a.tb[s];
+    // (the loop wakes neither, a re-uploaded bin may have become one)
+    if (bin == kTimeBinInhibited || a.perm[s] >= a.n_owned) continue;
+    float4 vf = vfull[s];
+    float4 ac = a.acc[s];
+    const float4 ag = agrav[s];
+    float v[3] = {vf.x, vf.y, vf.z};
+    const float ah[3] = {ac.x, ac.y, ac.z}, g3[3] = {ag.x, ag.y, ag.z};
+    float u_full = vf.w, u_dt = ac.w;
+    const LimitedPart r = limiter_limit_part(K, bin, w, v, &u_full, &u_dt, ah, g3, hasg[s] != 0);
+    a.tb[s] = (int8_t)r.new_bin;
+    if (r.was_active) {
+      n_act++;
+    } else {
+      n_inact++;
+      vfull[s] = make_float4(v[0], v[1], v[2], u_full);
+      if (u_dt != ac.w) {  // u_dt = 0 at the energy floor
+        ac.w = u_dt;
+        a.acc[s] = ac;
+      }
+      vmax = fmaxf(vmax, sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+    }
+    const long long c = kMaxNrTimesteps - r.ti_end_new;
+    end_min_c = c > end_min_c ? c : end_min_c;
+    end_max = r.ti_end_new > end_max ? r.ti_end_new : end_max;
+    beg_max = r.ti_beg_new > beg_max ? r.ti_beg_new : beg_max;
+    const unsigned int bc = (unsigned int)(127 - r.new_bin);
+    min_bin_c = bc > min_bin_c ? bc : min_bin_c;
+  }
+  const int wv = (int)(threadIdx.x >> 6);
+  const bool lead = (threadIdx.x & 63) == 0;
+  end_min_c = wave_max_ll(end_min_c);
+  end_max = wave_max_ll(end_max);
+  beg_max = wave_max_ll(beg_max);
+  n_act = wave_sum_u(n_act);
+  n_inact = wave_sum_u(n_inact);
+  min_bin_c = wave_max_u(min_bin_c);
+  for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
+  if (lead) {
+    sm_t[0][wv] = end_min_c;
+    sm_t[1][wv] = end_max;
+    sm_t[2][wv] = beg_max;
+    sm_c[0][wv] = n_act;
+    sm_c[1][wv] = n_inact;
+    sm_c[2][wv] = min_bin_c;
+    sm_v[wv] = vmax;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const unsigned int na = sm_c[0][0] + sm_c[0][1] + sm_c[0][2] + sm_c[0][3];
+  const unsigned int ni = sm_c[1][0] + sm_c[1][1] + sm_c[1][2] + sm_c[1][3];
+  if (na + ni == 0u) return;  // nothing woken in this block
+  for (int k = 0; k < 3; k++) {
+    long long m = sm_t[k][0];
+    for (int j = 1; j < 4; j++) m = sm_t[k][j] > m ? sm_t[k][j] : m;
+    if (m > 0) atomic_max_u64_if(rec + REC_END_MIN + k, (unsigned long long)m);
+  }
+  if (na) atomicAdd(lim + LIM_N_ACTIVE, na);
+  if (ni) atomicAdd(lim + LIM_N_INACTIVE, ni);
+  const unsigned int mb = max(max(sm_c[2][0], sm_c[2][1]), max(sm_c[2][2], sm_c[2][3]));
+  atomic_max_bits_if(lim + LIM_MIN_BIN_C, mb);
+  const float m = fmaxf(fmaxf(sm_v[0], sm_v[1]), fmaxf(sm_v[2], sm_v[3]));
+  if (m > 0.f) atomic_max_u64_if(rec + REC_VMAX, (unsigned long long)__float_as_uint(m));
+}
+
+swh_status fill_limiter(const swh_limiter_params* L, LimiterKicks* d) {
+  const double* fh[3] = {L->first_half_hydro, L->first_half_grav, L->first_half_therm};
+  const double* sb[3] = {L->since_begin_hydro, L->since_begin_grav, L->since_begin_therm};
+  d->ti_current = L->ti_current;
+  d->time_base = L->time_base;
+  d->max_active_bin = L->max_active_bin;
+  d->min_u = L->min_u;
+  for (int k = 0; k < 3; k++) {
+    if ((fh[k] == nullptr) != (sb[k] == nullptr)) {
+      set_error("swh_limiter_params: first_half and since_begin of a kind go together");
+      return SWH_ERR_ARG;
+    }
+    d->has[k] = fh[k] != nullptr;
+    for (int b = 0; b < kLimiterBins; b++) {
+      d->first_half[k][b] = fh[k] ? fh[k][b] : 0.;
+      d->since_begin[k][b] = sb[k] ? sb[k][b] : 0.;
+    }
+  }
+  return SWH_OK;
+}
+
+// The wake-up words in sorted order: gathered from the caller-order copy a
+// rebuild left, or all not awake.
+swh_status ensure_wake(swh_space* s) {
+  if (s->wake_sorted) return SWH_OK;
+  SWH_TRY(s->wake_s.reserve((size_t)s->n * sizeof(int)));
+  const int grid = (int)((s->n + 255) / 256);
+  if (s->wake_caller)
+    hipLaunchKernelGGL(wake_sort_kernel, dim3(grid), dim3(256), 0, s->stream,
+                       s->perm.as<const int>(), s->wake_c.as<const int>(), s->n,
+                       s->wake_s.as<int>());
+  else
+    hipLaunchKernelGGL(wake_fill_kernel, dim3(grid), dim3(256), 0, s->stream, s->wake_s.as<int>(),
+                       s->n);
+  SWH_HIP(hipGetLastError());
+  s->wake_sorted = true;
+  s->wake_caller = false;
+  return SWH_OK;
+}
+
+swh_status not_linked(const swh_space* s, const char* what) {
+  if (!s->link) return SWH_OK;
+  set_error("%s: the space is linked to a gspace; the limiter of a coupled step must also hand "
+            "the new time bin to the gas gpart, which is not built",
+            what);
+  return SWH_ERR_STATE;
+}
+
+swh_status apply_ready(swh_space* s, const char* what) {
+  if (!s->xparts_valid) {
+    set_error("swh_space_upload_xparts must precede %s", what);
+    return SWH_ERR_STATE;
+  }
+  if (!s->has_ufull) {
+    set_error("%s needs u_full in the uploaded xparts (swh_xpart_layout.off_u_full)", what);
+    return SWH_ERR_ARG;
+  }
+  if (!s->built) {
+    set_error("swh_space_rebuild must precede %s", what);
+    return SWH_ERR_STATE;
+  }
+  if (!s->step_has_ts) {
+    set_error("swh_space_timestep must precede %s: it merges into the time step's record", what);
+    return SWH_ERR_STATE;
+  }
+  return SWH_OK;
+}
+
+swh_status limiter_loop(swh_space* s, const swh_hydro_params* P) {
+  if (!s->built) {
+    set_error("swh_space_rebuild must precede the limiter loop");
+    return SWH_ERR_STATE;
+  }
+  SWH_HIP(hipSetDevice(s->ctx->device));
+  SWH_TRY(ensure_wake(s));
+  return space_limiter_walk(s, P);
+}
+
+swh_status limiter_apply(swh_space* s, const swh_limiter_params* L, const swh_hydro_params* P,
+                         const char* what) {
+  if (L->max_active_bin != P->max_active_bin) {
+    set_error("%s: max_active_bin of the limiter (%d) and the hydro parameters (%d) differ", what,
+              (int)L->max_active_bin, (int)P->max_active_bin);
+    return SWH_ERR_ARG;
+  }
+  LimiterKicks K;
+  SWH_TRY(fill_limiter(L, &K));
+  SWH_TRY(apply_ready(s, what));
+  SWH_HIP(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->stream;
+  SWH_TRY(space_ensure_xsorted(s));
+  SWH_TRY(ensure_wake(s));
+  SWH_TRY(s->lim_rec.reserve(LIM_SLOTS * sizeof(unsigned int)));
+  SWH_TRY(s->lim_host.reserve(LIM_SLOTS * sizeof(unsigned int)));
+  if (!s->lim_event) SWH_HIP(hipEventCreateWithFlags(&s->lim_event, hipEventDisableTiming));
+  SWH_HIP(hipMemsetAsync(s->lim_rec.ptr, 0, LIM_SLOTS * sizeof(unsigned int), st));
+  unsigned long long* rec = s->step_rec.as<unsigned long long>();
+  const int grid = (int)std::min<int64_t>((s->n + 255) / 256, 4 * kReduceBlocks);
+  hipLaunchKernelGGL(limiter_apply_kernel, dim3(grid), dim3(256), 0, st, soa_of(s),
+                     s->vfull_s.as<float4>(), s->agrav_s.as<const float4>(),
+                     s->hasg_s.as<const int8_t>(), s->wake_s.as<int>(), s->n, K, rec,
+                     s->lim_rec.as<unsigned int>());
+  SWH_HIP(hipGetLastError());
+  SWH_HIP(hipMemcpyAsync(s->lim_host.ptr, s->lim_rec.ptr, LIM_SLOTS * sizeof(unsigned int),
+                         hipMemcpyDeviceToHost, st));
+  SWH_HIP(hipEventRecord(s->lim_event, st));
+  s->lim_has = true;
+  // the merged step record, as every launch of the step kernel leaves it
+  SWH_HIP(hipMemcpyAsync(s->step_host.ptr, rec, REC_SLOTS * sizeof(unsigned long long),
+                         hipMemcpyDeviceToHost, st));
+  SWH_HIP(hipEventRecord(s->step_event, st));
+  s->step_pending = true;
+  // a woken particle may have entered the active bins without a list
+  s->list_valid = false;
+  s->list_check = false;
+  return SWH_OK;
+}
+
+}  // namespace
+
+// Before a re-sort: the words go to caller order (ensure_wake gathers them
+// again under the new order).
+swh_status space_wakeup_to_caller(swh_space* s) {
+  if (!s->wake_sorted || s->n == 0) return SWH_OK;
+  SWH_TRY(s->wake_c.reserve((size_t)s->n * sizeof(int)));
+  hipLaunchKernelGGL(wake_unsort_kernel, dim3((int)((s->n + 255) / 256)), dim3(256), 0, s->stream,
+                     s->perm.as<const int>(), s->wake_s.as<const int>(), s->n,
+                     s->wake_c.as<int>());
+  SWH_HIP(hipGetLastError());
+  s->wake_sorted = false;
+  s->wake_caller = true;
+  return SWH_OK;
+}
+
+void limiter_release(swh_space* s) {
+  s->wake_s.release();
+  s->wake_c.release();
+  s->lim_rec.release();
+  s->lim_host.release();
+  if (s->lim_event) (void)hipEventDestroy(s->lim_event);
+  s->lim_event = nullptr;
+}
+
+}  // namespace swh
+
+using namespace swh;
+
+extern "C" {
+
+swh_status swh_space_limiter_loop(swh_space* s, const swh_hydro_params* P) {
+  if (!s || !P) return SWH_ERR_ARG;
+  SWH_TRY(not_linked(s, "swh_space_limiter_loop"));
+  if (s->n == 0) return SWH_OK;
+  return limiter_loop(s, P);
+}
+
+swh_status swh_space_download_wakeup(swh_space* s, int8_t* out, int on_device) {
+  if (!s || (s->n > 0 && !out)) return SWH_ERR_ARG;
+  if (s->n == 0) return SWH_OK;
+  SWH_HIP(hipSetDevice(s->ctx->device));
+  hipStream_t st = s->stream;
+  SWH_TRY(s->tmp_soa.reserve((size_t)s->n));
+  const int* perm = s->wake_sorted ? s->perm.as<const int>() : nullptr;
+  const int* wake = s->wake_sorted   ? s->wake_s.as<const int>()
+                    : s->wake_caller ? s->wake_c.as<const int>()
+                                     : nullptr;
+  hipLaunchKernelGGL(wake_pack_kernel, dim3((int)((s->n + 255) / 256)), dim3(256), 0, st, perm,
+                     wake, s->n, s->tmp_soa.as<int8_t>());
+  SWH_HIP(hipGetLastError());
+  SWH_HIP(hipMemcpyAsync(out, s->tmp_soa.ptr, (size_t)s->n,
+                         on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  SWH_HIP(hipStreamSynchronize(st));
+  return SWH_OK;
+}
+
+swh_status swh_space_limiter_apply(swh_space* s, const swh_limiter_params* L,
+                                   const swh_hydro_params* P) {
+  if (!s || !L || !P) return SWH_ERR_ARG;
+  SWH_TRY(not_linked(s, "swh_space_limiter_apply"));
+  if (s->n == 0) return SWH_OK;
+  return limiter_apply(s, L, P, "swh_space_limiter_apply");
+}
+
+swh_status swh_space_end_step_limited(swh_space* s, const swh_kick_params* K2,
+                                      const swh_timestep_params* T, const swh_kick_params* K1,
+                                      const swh_limiter_params* L, const swh_hydro_params* P) {
+  const char* what = "swh_space_end_step_limited";
+  if (!s || !K2 || !T || !K1 || !L || !P) return SWH_ERR_ARG;
+  SWH_TRY(not_linked(s, what));
+  if (s->n == 0) return SWH_OK;
+  // kick2 + timestep in one launch; the pair lists of the step stay: they hold
+  // the active particles, which are the starting ones whatever their new bins
+  SWH_TRY(space_kick2_timestep_keep_lists(s, K2, T, P, what));
+  swh_status r = limiter_loop(s, P);
+  if (r == SWH_OK) r = limiter_apply(s, L, P, what);
+  if (r == SWH_OK) r = space_kick1(s, K1, P, what);
+  s->list_valid = false;  // the bins the lists were built with are gone
+  s->list_check = false;
+  return r;
+}
+
+swh_status swh_space_limiter_result(swh_space* s, swh_limiter_result* out) {
+  if (!s || !out) return SWH_ERR_ARG;
+  out->n_woken_active = out->n_woken_inactive = 0;
+  out->min_new_bin = SWH_NUM_TIME_BINS + 1;
+  out->reserved = 0;
+  if (s->n == 0) return SWH_OK;
+  if (!s->lim_has) {
+    set_error("swh_space_limiter_apply or swh_space_end_step_limited must precede "
+              "swh_space_limiter_result");
+    return SWH_ERR_STATE;
+  }
+  SWH_HIP(hipSetDevice(s->ctx->device));
+  SWH_HIP(hipEventSynchronize(s->lim_event));
+  const unsigned int* h = static_cast<const unsigned int*>(s->lim_host.ptr);
+  out->n_woken_active = (int64_t)h[LIM_N_ACTIVE];
+  out->n_woken_inactive = (int64_t)h[LIM_N_INACTIVE];
+  if (h[LIM_N_ACTIVE] + h[LIM_N_INACTIVE] > 0) out->min_new_bin = 127 - (int32_t)h[LIM_MIN_BIN_C];
+  return SWH_OK;
+}
+
+}  // extern "C"

@@ -73,6 +73,23 @@ swh_status space_xparts_to_caller(swh_space* s);
 // swh_kick.hip: wait for the latest step record, if one is queued, and take
 // its max |v_full| as the drift's displacement bound.
 swh_status space_fetch_step_record(swh_space* s);
+// Record slots of the step kernel (u64 each, all reduced by atomicMax /
+// atomicAdd from zero; REC_END_MIN holds max_nr_timesteps - ti_end_min). The
+// limiter's apply stage merges into the first three and REC_VMAX.
+enum { REC_END_MIN = 0, REC_END_MAX, REC_BEG_MAX, REC_UPDATED, REC_BELOW, REC_VMAX, REC_SLOTS = 8 };
+// swh_kick.hip: kick2 + timestep in one launch that keeps the pair lists (the
+// limiter walks them before they are dropped), and kick1.
+swh_status space_kick2_timestep_keep_lists(swh_space* s, const swh_kick_params* K2,
+                                           const swh_timestep_params* T,
+                                           const swh_hydro_params* P, const char* what);
+swh_status space_kick1(swh_space* s, const swh_kick_params* K1, const swh_hydro_params* P,
+                       const char* what);
+// swh_hydro.hip: the limiter's neighbour loop over the step's pair lists
+// (built if there are none) into the sorted wake-up words (s->wake_s).
+swh_status space_limiter_walk(swh_space* s, const swh_hydro_params* P);
+// swh_limiter.hip: the wake-up words before / after a re-sort (swh_space_rebuild)
+swh_status space_wakeup_to_caller(swh_space* s);
+void limiter_release(swh_space* s);
 // Recompute max h over the set into the device slot counters[2] (float bits).
 swh_status space_hmax_to_device(swh_space* s);
 

@@ -750,6 +750,7 @@ swh_status swh_space_destroy(swh_space* s) {
                     &s->step_rec};
   for (DevBuf* b : bufs) b->release();
   couple_release(s);
+  limiter_release(s);
   s->step_host.release();
   if (s->step_event) (void)hipEventDestroy(s->step_event);
   s->hstage.release();
@@ -946,6 +947,8 @@ swh_status swh_space_upload_parts(swh_space* s, const void* parts, int64_t count
   s->xsorted_valid = false;
   s->step_pending = false;
   s->step_has_ts = false;
+  s->wake_sorted = s->wake_caller = false;  // every particle starts not awake
+  s->lim_has = false;
   s->grid.dx = 0.;
   hipLaunchKernelGGL(unpack_kernel, dim3(grid), dim3(block), 0, s->stream, L,
                      s->aos.as<const char>(), count, soa_of(s), s->hasg_c.as<int8_t>());
@@ -1033,6 +1036,7 @@ swh_status swh_space_rebuild(swh_space* s, const swh_hydro_params* P, double min
   // first and are gathered again by the next drift or kick
   SWH_TRY(space_xparts_to_caller(s));
   s->xsorted_valid = false;
+  SWH_TRY(space_wakeup_to_caller(s));  // the limiter's wake-up words follow the re-sort too
   s->gp_pulled = false;  // the pulled accelerations were in the old order
   // 1. bounding box + max h
   const int nb = 512;

@@ -237,5 +237,9 @@ __device__ __forceinline__ void reduce_lanes(LoopState<LOOP_FORCE, T>& s) {
     s.n += __shfl_xor(s.n, o);
   }
 }
+template <int W, typename T>  // (the wake-ups are already in memory)
+__device__ __forceinline__ void reduce_lanes(LoopState<LOOP_LIMITER, T>& s) {
+  for (int o = 1; o < W; o <<= 1) s.n += __shfl_xor(s.n, o);
+}
 
 }  // namespace swh

@@ -8,7 +8,10 @@ the device from the first upload on.
     step()        engine_step: advance ti_current to the earliest end of a
                   step (the record's ti_end_min), drift everything there, run
                   the hydro chain on the active bins, then kick2 + timestep +
-                  kick1 in one launch (swh_space_end_step)
+                  kick1 in one launch (swh_space_end_step); with limiter=True
+                  (swift --limiter) the limited end of step instead
+                  (swh_space_end_step_limited): starting particles wake the
+                  neighbours more than two bins above them before kick1
 
 The only host synchronisation of a step is the record read (step_result): it
 delivers ti_end_min, which chooses the next ti_current, and max |v_full|,
@@ -44,7 +47,7 @@ def get_max_active_bin(ti: int) -> int:
 class Integrator:
     def __init__(self, space, P: abi.HydroParams, T: abi.TimestepParams, time_base: float = None,
                  min_u: float = 0.0, cosmology: "cosmo_mod.Cosmology" = None,
-                 max_rel_dx: float = 0.1):
+                 max_rel_dx: float = 0.1, limiter: bool = False):
         if cosmology is None and not time_base:
             raise ValueError("a non-cosmological run needs time_base (time per tick)")
         self.sp = space
@@ -59,6 +62,9 @@ class Integrator:
         self.result = None
         self.rebuilds = 0
         self.chain = None  # interaction counts of the last hydro chain
+        self.limiter = bool(limiter)
+        # running counts of the limited steps (limiter=True)
+        self.limited = {"n_woken_active": 0, "n_woken_inactive": 0, "min_new_bin": None}
         self.P.time_base = self.time_base
         self.T.time_base_inv = 1.0 / self.time_base
 
@@ -90,6 +96,16 @@ class Integrator:
         if self.cosmology is not None:
             K.set_tables(**cosmo_mod.kick_tables(self.cosmology, self.ti_current, kick))
         return K
+
+    def _limiter_params(self) -> abi.LimiterParams:
+        L = abi.LimiterParams()
+        L.ti_current = self.ti_current
+        L.time_base = self.time_base
+        L.max_active_bin = self.max_active_bin
+        L.min_u = self.min_u
+        if self.cosmology is not None:
+            L.set_tables(*cosmo_mod.limiter_tables(self.cosmology, self.ti_current))
+        return L
 
     def _drift_params(self, ti_old: int, ti_new: int) -> abi.DriftParams:
         cm = self.cosmology
@@ -143,8 +159,22 @@ class Integrator:
         return self.chain
 
     def end_step(self) -> dict:
-        self.sp.end_step(self._kick_params(2), self.T, self._kick_params(1), self.P)
+        if not self.limiter:
+            self.sp.end_step(self._kick_params(2), self.T, self._kick_params(1), self.P)
+            self.result = self.sp.step_result()
+            return self.result
+        # (init_step needs no limiter: every particle starts together in bin
+        # 0, so there is nothing to wake)
+        self.sp.end_step_limited(self._kick_params(2), self.T, self._kick_params(1),
+                                 self._limiter_params(), self.P)
         self.result = self.sp.step_result()
+        r = self.sp.limiter_result()
+        self.limited["n_woken_active"] += r["n_woken_active"]
+        self.limited["n_woken_inactive"] += r["n_woken_inactive"]
+        if r["n_woken_active"] + r["n_woken_inactive"] > 0:
+            old = self.limited["min_new_bin"]
+            self.limited["min_new_bin"] = (r["min_new_bin"] if old is None
+                                           else min(old, r["min_new_bin"]))
         return self.result
 
     def step(self) -> dict:

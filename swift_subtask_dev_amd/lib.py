@@ -62,6 +62,8 @@ HIP_SYMBOLS = [
     "swh_space_link_gspace", "swh_space_pull_gravity", "swh_space_push_gparts",
     "swh_space_kick1_linked", "swh_space_kick2_linked", "swh_space_timestep_linked",
     "swh_space_end_step_linked", "swh_space_link_times",
+    "swh_space_limiter_loop", "swh_space_download_wakeup", "swh_space_limiter_apply",
+    "swh_space_end_step_limited", "swh_space_limiter_result",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -210,6 +212,13 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
         "swh_space_end_step_linked": (C.c_int, [vp, P(abi.KickParams), P(abi.TimestepParams),
                                                 P(abi.KickParams), P(abi.HydroParams), dp, dp]),
         "swh_space_link_times": (C.c_int, [vp, P(C.c_float)]),
+        "swh_space_limiter_loop": (C.c_int, [vp, P(abi.HydroParams)]),
+        "swh_space_download_wakeup": (C.c_int, [vp, vp, C.c_int]),
+        "swh_space_limiter_apply": (C.c_int, [vp, P(abi.LimiterParams), P(abi.HydroParams)]),
+        "swh_space_end_step_limited": (C.c_int, [vp, P(abi.KickParams), P(abi.TimestepParams),
+                                                 P(abi.KickParams), P(abi.LimiterParams),
+                                                 P(abi.HydroParams)]),
+        "swh_space_limiter_result": (C.c_int, [vp, P(abi.LimiterResult)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -505,6 +514,43 @@ class HydroSpace:
         return {"ti_end_min": r.ti_end_min, "ti_end_max": r.ti_end_max,
                 "ti_beg_max": r.ti_beg_max, "n_updated": r.n_updated,
                 "n_below_dt_min": r.n_below_dt_min, "vfull_max": r.vfull_max}
+
+    # ---- time-step limiter (swh_limiter.hip) -------------------------------
+    def limiter_loop(self, P: abi.HydroParams):
+        """The limiter neighbour loop: starting particles wake the neighbours
+        more than two bins above them. Enqueue only."""
+        _check(self._lib.swh_space_limiter_loop(self.handle, C.byref(P)), "limiter_loop",
+               self._lib)
+
+    def download_wakeup(self) -> np.ndarray:
+        """The wake-up of every particle (int8, caller order;
+        abi.TIME_BIN_NOT_AWAKE where none)."""
+        out = np.empty(self._lib.swh_space_count(self.handle), dtype=np.int8)
+        _check(self._lib.swh_space_download_wakeup(self.handle, _ptr(out), 0), "download_wakeup",
+               self._lib)
+        return out
+
+    def limiter_apply(self, L: abi.LimiterParams, P: abi.HydroParams):
+        """runner_do_limiter: woken particles get their new bin (inactive ones
+        are re-kicked); merges into the step record."""
+        _check(self._lib.swh_space_limiter_apply(self.handle, C.byref(L), C.byref(P)),
+               "limiter_apply", self._lib)
+
+    def end_step_limited(self, K2: abi.KickParams, T: abi.TimestepParams, K1: abi.KickParams,
+                         L: abi.LimiterParams, P: abi.HydroParams):
+        """kick2 + timestep, the limiter loop on the step's pair lists, the
+        apply stage and kick1."""
+        _check(self._lib.swh_space_end_step_limited(self.handle, C.byref(K2), C.byref(T),
+                                                    C.byref(K1), C.byref(L), C.byref(P)),
+               "end_step_limited", self._lib)
+
+    def limiter_result(self) -> dict:
+        """Counts of the last limiter_apply / end_step_limited (waits for it)."""
+        r = abi.LimiterResult()
+        _check(self._lib.swh_space_limiter_result(self.handle, C.byref(r)), "limiter_result",
+               self._lib)
+        return {"n_woken_active": r.n_woken_active, "n_woken_inactive": r.n_woken_inactive,
+                "min_new_bin": r.min_new_bin}
 
     def drift(self, D: abi.DriftParams, P: abi.HydroParams):
         _check(self._lib.swh_space_drift(self.handle, C.byref(D), C.byref(P)), "drift", self._lib)
