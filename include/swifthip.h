@@ -494,8 +494,8 @@ SWH_API swh_status swh_space_upload_a_grav(swh_space *s, const float *a_grav, in
 /* The wake-up of every particle lives on the device from the upload   */
 /* of the parts on (not awake) and follows swh_space_rebuild's         */
 /* re-sort; it is not part of swh_part_layout. All calls only enqueue. */
-/* A space linked to a gspace gets SWH_ERR_STATE: the coupled step's   */
-/* limiter must also hand the new bin to the gas gpart.                */
+/* A space linked to a gspace gets SWH_ERR_STATE from these three: its */
+/* limiter is swh_space_limiter_loop_linked and its kin, below.        */
 /* runner_do_sync (limiter_data.to_be_synchronized) is not built.      */
 /* ------------------------------------------------------------------ */
 typedef struct swh_limiter_params {
@@ -1013,6 +1013,40 @@ SWH_API swh_status swh_space_end_step_linked(swh_space *s, const swh_kick_params
                                              const swh_timestep_params *T,
                                              const swh_kick_params *K1, const swh_hydro_params *P,
                                              double dt_kick_mesh2, double dt_kick_mesh1);
+/* The time-step limiter of a linked space (the coupled step under swift
+ * --limiter): swh_space_limiter_loop / _limiter_apply / _end_step_limited with
+ * the linked kicks and time step in the place of the plain ones. The loop is
+ * the same walk into the same wake-up words (swh_space_download_wakeup). The
+ * apply stage differs in one place: a linked particle's gravity kick uses
+ * p->gpart->a_grav, here the pulled array, not the space's xp->a_grav (in a
+ * linked space a_grav + a_grav_mesh of the last kick1, the drift's
+ * acceleration); the gpart flag is the link's, so a part no gas gpart names
+ * takes swh_space_limiter_apply's path without a gravity term. The mesh kick
+ * is 0 in all three kicks of timestep_limit_part (the reference passes
+ * dt_kick_mesh_grav = 0: "we can't go back more than one global step").
+ * swh_space_end_step_limited_linked is the linked kick2 + time step in one
+ * launch with the pair lists kept, the loop on those lists, the linked apply,
+ * the linked kick1, and only then the lists dropped: the same bits as
+ * swh_space_kick2_linked, _timestep_linked, _limiter_loop_linked,
+ * _limiter_apply_linked, _kick1_linked in turn.
+ * SWH_ERR_STATE without a link, and without a swh_space_pull_gravity since the
+ * last rebuild or upload; the apply's other preconditions, the cosmological
+ * tables, the reset of the words, the merge into the step record (the
+ * gspace's record does not count gas gparts, so this is the whole merge),
+ * swh_space_limiter_result and the dropped lists are swh_space_limiter_apply's.
+ * The reference's runner_do_limiter also sets p->gpart->time_bin, and
+ * kick_part p->gpart->v_full. Here both stay the caller's
+ * swh_space_push_gparts(SWH_PUSH_V_FULL | SWH_PUSH_TIME_BIN) after the stage,
+ * exactly as for the linked kicks and time step: the space holds no part ->
+ * record index, and the records move with every tree build. No stage here
+ * writes a byte of the gspace. */
+SWH_API swh_status swh_space_limiter_loop_linked(swh_space *s, const swh_hydro_params *P);
+SWH_API swh_status swh_space_limiter_apply_linked(swh_space *s, const swh_limiter_params *L,
+                                                  const swh_hydro_params *P);
+SWH_API swh_status swh_space_end_step_limited_linked(
+    swh_space *s, const swh_kick_params *K2, const swh_timestep_params *T,
+    const swh_kick_params *K1, const swh_limiter_params *L, const swh_hydro_params *P,
+    double dt_kick_mesh2, double dt_kick_mesh1);
 /* Device time of the last launch of each linked stage (ms, HIP events on the
  * stream the stage runs on; waits for them): ms[0..3) = pull, push, the last
  * linked kick1 / kick2 / timestep / end_step. -1 for a stage not yet run. */

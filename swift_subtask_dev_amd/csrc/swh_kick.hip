@@ -452,6 +452,18 @@ swh_status space_kick1(swh_space* s, const swh_kick_params* K1, const swh_hydro_
   return launch_step<false, false, true>(s, nullptr, nullptr, K1, P, what);
 }
 
+swh_status space_kick2_timestep_keep_lists_linked(swh_space* s, const swh_kick_params* K2,
+                                                  const swh_timestep_params* T,
+                                                  const swh_hydro_params* P, const char* what,
+                                                  double dt_mesh2) {
+  return launch_step<true, true, false, true>(s, K2, T, nullptr, P, what, dt_mesh2, 0., true);
+}
+
+swh_status space_kick1_linked(swh_space* s, const swh_kick_params* K1, const swh_hydro_params* P,
+                              const char* what, double dt_mesh1) {
+  return launch_step<false, false, true, true>(s, nullptr, nullptr, K1, P, what, 0., dt_mesh1);
+}
+
 // The latest record's max |v_full| bounds the next drift's displacement.
 swh_status space_fetch_step_record(swh_space* s) {
   if (!s->step_pending) return SWH_OK;

@@ -10,7 +10,10 @@
 // holds the wake-up words, the per-particle apply stage -- the arithmetic is
 // swh_limiter.h's, shared with a plain host program -- and the C entries,
 // among them the fused end of step that walks the pair lists before the time
-// step's new bins make them void.
+// step's new bins make them void. A space linked to a gspace has its own
+// entries (_linked): the same loop, the apply kernel's LK instantiation, which
+// kicks a linked particle with its gpart's pulled a_grav, and the linked kicks
+// and time step of swh_kick.hip around them.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -81,6 +84,11 @@ __device__ __forceinline__ void atomic_max_u64_if(unsigned long long* p, unsigne
 // ti_end_new / ti_beg_new merged into the step record (min into ti_end_min --
 // kept as max_nr_timesteps - ti_end -- max into ti_end_max and ti_beg_max,
 // max |v_full| of the re-kicked particles into the drift's bound).
+// LK: the space is linked to a gspace (as step_kernel's LK): hasg is the link
+// flag and agrav the pulled array, p->gpart->a_grav, read for the linked
+// particles only (the others' rows were never written); the mesh kick is 0 in
+// all three kicks, as the reference passes it.
+template <bool LK>
 __global__ __launch_bounds__(256) void limiter_apply_kernel(
     SoA a, float4* __restrict__ vfull, const float4* __restrict__ agrav,
     const int8_t* __restrict__ hasg, int* __restrict__ wake, int64_t n, LimiterKicks K,
@@ -101,7 +109,13 @@ __global__ __launch_bounds__(256) void limiter_apply_kernel(
     if (bin == kTimeBinInhibited || a.perm[s] >= a.n_owned) continue;
     float4 vf = vfull[s];
     float4 ac = a.acc[s];
-    const float4 ag = agrav[s];
+    float4 ag;
+    if (LK) {
+      ag = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (hasg[s] != 0) ag = agrav[s];
+    } else {
+      ag = agrav[s];
+    }
     float v[3] = {vf.x, vf.y, vf.z};
     const float ah[3] = {ac.x, ac.y, ac.z}, g3[3] = {ag.x, ag.y, ag.z};
     float u_full = vf.w, u_dt = ac.w;
@@ -203,9 +217,9 @@ swh_status ensure_wake(swh_space* s) {
 
 swh_status not_linked(const swh_space* s, const char* what) {
   if (!s->link) return SWH_OK;
-  set_error("%s: the space is linked to a gspace; the limiter of a coupled step must also hand "
-            "the new time bin to the gas gpart, which is not built",
-            what);
+  set_error("%s: the space is linked to a gspace; the limiter of a coupled step reads the gas "
+            "gpart's a_grav: use %s_linked",
+            what, what);
   return SWH_ERR_STATE;
 }
 
@@ -239,6 +253,23 @@ swh_status limiter_loop(swh_space* s, const swh_hydro_params* P) {
   return space_limiter_walk(s, P);
 }
 
+// The entries for a linked space: a link, and (past the empty space) this
+// step's gravity pulled, as the linked kicks ask.
+swh_status need_link(const swh_space* s, const char* what) {
+  if (s->link) return SWH_OK;
+  set_error("swh_space_link_gspace must precede %s", what);
+  return SWH_ERR_STATE;
+}
+
+swh_status need_pull(const swh_space* s, const char* what) {
+  if (s->gp_pulled) return SWH_OK;
+  set_error("%s: no swh_space_pull_gravity since the last rebuild or upload", what);
+  return SWH_ERR_STATE;
+}
+
+// LK: the linked stage, the pulled a_grav of the gas gparts in the place of
+// xp->a_grav (in a linked space that is a_grav + a_grav_mesh of the last kick1)
+template <bool LK>
 swh_status limiter_apply(swh_space* s, const swh_limiter_params* L, const swh_hydro_params* P,
                          const char* what) {
   if (L->max_active_bin != P->max_active_bin) {
@@ -259,9 +290,10 @@ swh_status limiter_apply(swh_space* s, const swh_limiter_params* L, const swh_hy
   SWH_HIP(hipMemsetAsync(s->lim_rec.ptr, 0, LIM_SLOTS * sizeof(unsigned int), st));
   unsigned long long* rec = s->step_rec.as<unsigned long long>();
   const int grid = (int)std::min<int64_t>((s->n + 255) / 256, 4 * kReduceBlocks);
-  hipLaunchKernelGGL(limiter_apply_kernel, dim3(grid), dim3(256), 0, st, soa_of(s),
-                     s->vfull_s.as<float4>(), s->agrav_s.as<const float4>(),
-                     s->hasg_s.as<const int8_t>(), s->wake_s.as<int>(), s->n, K, rec,
+  const float4* agrav = LK ? s->gp_agrav_s.as<const float4>() : s->agrav_s.as<const float4>();
+  hipLaunchKernelGGL((limiter_apply_kernel<LK>), dim3(grid), dim3(256), 0, st, soa_of(s),
+                     s->vfull_s.as<float4>(), agrav, s->hasg_s.as<const int8_t>(),
+                     s->wake_s.as<int>(), s->n, K, rec,
                      s->lim_rec.as<unsigned int>());
   SWH_HIP(hipGetLastError());
   SWH_HIP(hipMemcpyAsync(s->lim_host.ptr, s->lim_rec.ptr, LIM_SLOTS * sizeof(unsigned int),
@@ -341,7 +373,47 @@ swh_status swh_space_limiter_apply(swh_space* s, const swh_limiter_params* L,
   if (!s || !L || !P) return SWH_ERR_ARG;
   SWH_TRY(not_linked(s, "swh_space_limiter_apply"));
   if (s->n == 0) return SWH_OK;
-  return limiter_apply(s, L, P, "swh_space_limiter_apply");
+  return limiter_apply<false>(s, L, P, "swh_space_limiter_apply");
+}
+
+swh_status swh_space_limiter_loop_linked(swh_space* s, const swh_hydro_params* P) {
+  const char* what = "swh_space_limiter_loop_linked";
+  if (!s || !P) return SWH_ERR_ARG;
+  SWH_TRY(need_link(s, what));
+  if (s->n == 0) return SWH_OK;
+  SWH_TRY(need_pull(s, what));
+  return limiter_loop(s, P);
+}
+
+swh_status swh_space_limiter_apply_linked(swh_space* s, const swh_limiter_params* L,
+                                          const swh_hydro_params* P) {
+  const char* what = "swh_space_limiter_apply_linked";
+  if (!s || !L || !P) return SWH_ERR_ARG;
+  SWH_TRY(need_link(s, what));
+  if (s->n == 0) return SWH_OK;
+  SWH_TRY(need_pull(s, what));
+  return limiter_apply<true>(s, L, P, what);
+}
+
+swh_status swh_space_end_step_limited_linked(swh_space* s, const swh_kick_params* K2,
+                                             const swh_timestep_params* T,
+                                             const swh_kick_params* K1,
+                                             const swh_limiter_params* L,
+                                             const swh_hydro_params* P, double dt_kick_mesh2,
+                                             double dt_kick_mesh1) {
+  const char* what = "swh_space_end_step_limited_linked";
+  if (!s || !K2 || !T || !K1 || !L || !P) return SWH_ERR_ARG;
+  SWH_TRY(need_link(s, what));
+  if (s->n == 0) return SWH_OK;
+  // (the launches check the pull) the pair lists of the step stay, as in
+  // swh_space_end_step_limited
+  SWH_TRY(space_kick2_timestep_keep_lists_linked(s, K2, T, P, what, dt_kick_mesh2));
+  swh_status r = limiter_loop(s, P);
+  if (r == SWH_OK) r = limiter_apply<true>(s, L, P, what);
+  if (r == SWH_OK) r = space_kick1_linked(s, K1, P, what, dt_kick_mesh1);
+  s->list_valid = false;  // the bins the lists were built with are gone
+  s->list_check = false;
+  return r;
 }
 
 swh_status swh_space_end_step_limited(swh_space* s, const swh_kick_params* K2,
@@ -355,7 +427,7 @@ swh_status swh_space_end_step_limited(swh_space* s, const swh_kick_params* K2,
   // the active particles, which are the starting ones whatever their new bins
   SWH_TRY(space_kick2_timestep_keep_lists(s, K2, T, P, what));
   swh_status r = limiter_loop(s, P);
-  if (r == SWH_OK) r = limiter_apply(s, L, P, what);
+  if (r == SWH_OK) r = limiter_apply<false>(s, L, P, what);
   if (r == SWH_OK) r = space_kick1(s, K1, P, what);
   s->list_valid = false;  // the bins the lists were built with are gone
   s->list_check = false;

@@ -84,6 +84,13 @@ swh_status space_kick2_timestep_keep_lists(swh_space* s, const swh_kick_params* 
                                            const swh_hydro_params* P, const char* what);
 swh_status space_kick1(swh_space* s, const swh_kick_params* K1, const swh_hydro_params* P,
                        const char* what);
+// the same two for a space linked to a gspace (step_kernel's LK flag)
+swh_status space_kick2_timestep_keep_lists_linked(swh_space* s, const swh_kick_params* K2,
+                                                  const swh_timestep_params* T,
+                                                  const swh_hydro_params* P, const char* what,
+                                                  double dt_mesh2);
+swh_status space_kick1_linked(swh_space* s, const swh_kick_params* K1, const swh_hydro_params* P,
+                              const char* what, double dt_mesh1);
 // swh_hydro.hip: the limiter's neighbour loop over the step's pair lists
 // (built if there are none) into the sorted wake-up words (s->wake_s).
 swh_status space_limiter_walk(swh_space* s, const swh_hydro_params* P);

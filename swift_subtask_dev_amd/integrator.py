@@ -390,7 +390,12 @@ class CoupledIntegrator(_GravityDriver):
                      and the gspace; push x; tree build; gravity on the
                      gspace's stream and the hydro chain on the space's; pull;
                      end_step_linked and the gspace's end_step; push v_full
-                     and time_bin; the two records
+                     and time_bin; the two records. With limiter=True (swift
+                     --limiter) end_step_limited_linked in the place of
+                     end_step_linked: starting gas particles wake the gas
+                     neighbours more than two bins above them before kick1;
+                     the push that follows hands the woken particles' new bin
+                     and v_full to their gparts
 
     P, T: the hydro side's abi.HydroParams / abi.TimestepParams (T's
     grav_dt_factor > 0 gives the gas its gravity time-step condition); G, GT:
@@ -403,7 +408,7 @@ class CoupledIntegrator(_GravityDriver):
                  G: abi.GravParams, GT: abi.GTimestepParams, time_base: float, cdim: int,
                  split_size: int = 64, max_depth: int = 12, box: float = 1.0,
                  const_G: float = 1.0, min_u: float = 0.0, max_rel_dx: float = 0.1,
-                 mesh: dict = None):
+                 mesh: dict = None, limiter: bool = False):
         if not time_base or time_base <= 0:
             raise ValueError("time_base (time per tick) must be positive")
         if T.dt_max != GT.dt_max:
@@ -427,6 +432,9 @@ class CoupledIntegrator(_GravityDriver):
         self.gas_mesh_kicks = 0  # half mesh kicks given to the gas so far
         self.n_linked = 0
         self.chain = None
+        self.limiter = bool(limiter)
+        # running counts of the limited steps (limiter=True), as Integrator.limited
+        self.limited = {"n_woken_active": 0, "n_woken_inactive": 0, "min_new_bin": None}
         self._reset_gravity()
 
     def _update_scalars(self):
@@ -535,10 +543,30 @@ class CoupledIntegrator(_GravityDriver):
         dt2, dt1 = self._mesh_kicks_here()
         self.gas_mesh_kicks += (dt2 != 0.0) + (dt1 != 0.0)
         K = self._kick_params()
-        self.sp.end_step_linked(K, self.T, K, self.P, dt2, dt1)
+        if not self.limiter:
+            self.sp.end_step_linked(K, self.T, K, self.P, dt2, dt1)
+            self.gs.end_step(self._gkick_params(dt2), self.GT, self._gkick_params(dt1))
+            self._push(v_full=True, time_bin=True)
+            return self._read_records()
+        # (init_step needs no limiter: everybody starts in bin 0.) The gspace
+        # neither kicks nor time-steps gas gparts and its record does not
+        # count them: the space's merged record is the whole merge, and the
+        # push hands the woken particles' bins and v_full to their gparts
+        L = abi.LimiterParams()
+        L.ti_current, L.time_base = self.ti_current, self.time_base
+        L.max_active_bin, L.min_u = self.max_active_bin, self.min_u
+        self.sp.end_step_limited_linked(K, self.T, K, L, self.P, dt2, dt1)
         self.gs.end_step(self._gkick_params(dt2), self.GT, self._gkick_params(dt1))
         self._push(v_full=True, time_bin=True)
-        return self._read_records()
+        self._read_records()
+        r = self.sp.limiter_result()
+        self.limited["n_woken_active"] += r["n_woken_active"]
+        self.limited["n_woken_inactive"] += r["n_woken_inactive"]
+        if r["n_woken_active"] + r["n_woken_inactive"] > 0:
+            old = self.limited["min_new_bin"]
+            self.limited["min_new_bin"] = (r["min_new_bin"] if old is None
+                                           else min(old, r["min_new_bin"]))
+        return self.result
 
     def step(self) -> dict:
         self.drift_to_next()

@@ -64,6 +64,8 @@ HIP_SYMBOLS = [
     "swh_space_end_step_linked", "swh_space_link_times",
     "swh_space_limiter_loop", "swh_space_download_wakeup", "swh_space_limiter_apply",
     "swh_space_end_step_limited", "swh_space_limiter_result",
+    "swh_space_limiter_loop_linked", "swh_space_limiter_apply_linked",
+    "swh_space_end_step_limited_linked",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -219,6 +221,13 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
                                                  P(abi.KickParams), P(abi.LimiterParams),
                                                  P(abi.HydroParams)]),
         "swh_space_limiter_result": (C.c_int, [vp, P(abi.LimiterResult)]),
+        "swh_space_limiter_loop_linked": (C.c_int, [vp, P(abi.HydroParams)]),
+        "swh_space_limiter_apply_linked": (C.c_int, [vp, P(abi.LimiterParams),
+                                                     P(abi.HydroParams)]),
+        "swh_space_end_step_limited_linked": (C.c_int, [vp, P(abi.KickParams),
+                                                        P(abi.TimestepParams), P(abi.KickParams),
+                                                        P(abi.LimiterParams), P(abi.HydroParams),
+                                                        dp, dp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -614,6 +623,28 @@ class HydroSpace:
         _check(self._lib.swh_space_end_step_linked(self.handle, C.byref(K2), C.byref(T),
                                                    C.byref(K1), C.byref(P), dt_mesh2, dt_mesh1),
                "end_step_linked", self._lib)
+
+    def limiter_loop_linked(self, P: abi.HydroParams):
+        """limiter_loop on a linked space (after pull_gravity): the same walk
+        into the same wake-up words."""
+        _check(self._lib.swh_space_limiter_loop_linked(self.handle, C.byref(P)),
+               "limiter_loop_linked", self._lib)
+
+    def limiter_apply_linked(self, L: abi.LimiterParams, P: abi.HydroParams):
+        """limiter_apply on a linked space: a linked particle's gravity kicks
+        use the pulled a_grav of its gpart, the mesh kick is 0. The new bins
+        and v_full reach the gparts with push_gparts(v_full, time_bin)."""
+        _check(self._lib.swh_space_limiter_apply_linked(self.handle, C.byref(L), C.byref(P)),
+               "limiter_apply_linked", self._lib)
+
+    def end_step_limited_linked(self, K2: abi.KickParams, T: abi.TimestepParams,
+                                K1: abi.KickParams, L: abi.LimiterParams, P: abi.HydroParams,
+                                dt_mesh2: float = 0.0, dt_mesh1: float = 0.0):
+        """The linked kick2 + timestep, the limiter loop on the step's pair
+        lists, the linked apply stage and the linked kick1."""
+        _check(self._lib.swh_space_end_step_limited_linked(
+            self.handle, C.byref(K2), C.byref(T), C.byref(K1), C.byref(L), C.byref(P), dt_mesh2,
+            dt_mesh1), "end_step_limited_linked", self._lib)
 
     def link_ms(self) -> dict:
         """HIP-event times (ms) of the last pull, push and linked kick /
