@@ -797,7 +797,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void p2
         sm[k] = (double)g.mass[gj];
         sb[k] = (unsigned char)bent[b];
       }
-      const double emax = act ? fmax(hi2, wave_max_f64(e2max)) : 0.;
+      // (the reduction outside the act test: every lane staged gparts, also
+      // the lanes past the leaf's count or of an inactive i, and a shuffle
+      // reads nothing from a lane that does not execute it)
+      const double tile_e2 = wave_max_f64(e2max);
+      const double emax = act ? fmax(hi2, tile_e2) : 0.;
       const bool wrap = periodic && __any(far);
       wave_sync();
       // The plain part [0, tA): no per-pair mask, the pairs counted per lane;
