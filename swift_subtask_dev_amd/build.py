@@ -37,7 +37,7 @@ HIP_SOURCES = ["swh_api.hip", "swh_tasks.hip", "swh_space.hip", "swh_hydro.hip",
                "swh_limiter.hip"]
 HIP_HEADERS = ["swh_internal.h", "swh_physics.h", "swh_space.h", "swh_gather.h", "swh_wave.h",
                "swh_list.h", "swh_mpole.h", "swh_timeline.h", "swh_gstep.h", "swh_couple.h",
-               "swh_limiter.h"]
+               "swh_limiter.h", "swh_steprec.h"]
 
 
 def _hipcc() -> str:

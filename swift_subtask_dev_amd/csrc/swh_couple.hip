@@ -19,15 +19,11 @@
 #include "swh_couple.h"
 #include "swh_internal.h"
 #include "swh_space.h"
+#include "swh_wave.h"
 
 namespace swh {
 
 enum { LC_LINKED = 0, LC_RANGE, LC_DUP, LC_INHIBITED, LC_SLOTS };
-
-__device__ __forceinline__ unsigned int cwave_sum_u(unsigned int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // Per record: a live gas gpart must name a part of [0, n) that no other names.
 // mark[j] counts the records that name part j (a vector atomic add).
@@ -48,9 +44,9 @@ __global__ __launch_bounds__(256) void link_mark_kernel(CoupleLayout L,
     linked++;
     if (atomicAdd(mark + j, 1) > 0) dup++;
   }
-  linked = cwave_sum_u(linked);
-  range = cwave_sum_u(range);
-  dup = cwave_sum_u(dup);
+  linked = wave_sum_u(linked);
+  range = wave_sum_u(range);
+  dup = wave_sum_u(dup);
   if ((threadIdx.x & 63) == 0) {
     if (linked) atomicAdd(cnt + LC_LINKED, linked);
     if (range) atomicAdd(cnt + LC_RANGE, range);
@@ -68,7 +64,7 @@ __global__ __launch_bounds__(256) void link_parts_kernel(const int* __restrict__
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
        s += (int64_t)gridDim.x * blockDim.x)
     if (mark[perm[s]] > 0 && tb[s] == kGpartBinInhibited) bad++;
-  bad = cwave_sum_u(bad);
+  bad = wave_sum_u(bad);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(cnt + LC_INHIBITED, bad);
 }
 
@@ -131,10 +127,6 @@ __global__ __launch_bounds__(256) void push_kernel(CoupleLayout L, char* __restr
   }
 }
 
-static bool cfloat3_ok(int off, int stride) {
-  return off >= 0 && off % 4 == 0 && off + 12 <= stride;
-}
-
 // Every offset the kernels use, compared with the stride.
 static swh_status couple_layout(const swh_gspace* g, CoupleLayout* out) {
   const GLayout& G = g->layout;
@@ -142,8 +134,8 @@ static swh_status couple_layout(const swh_gspace* g, CoupleLayout* out) {
   CoupleLayout L{G.stride, 0, G.x, S.off_v_full, G.a_grav, S.off_a_grav_mesh, G.time_bin,
                  S.off_type};
   if (L.stride < 8 || L.stride % 8 != 0 || L.x < 8 || L.x % 8 != 0 || L.x + 24 > L.stride ||
-      !cfloat3_ok(L.v_full, L.stride) || !cfloat3_ok(L.a_grav, L.stride) ||
-      !cfloat3_ok(L.a_grav_mesh, L.stride) || L.time_bin < 8 || L.time_bin >= L.stride ||
+      !float_field_ok(L.v_full, 3, L.stride) || !float_field_ok(L.a_grav, 3, L.stride) ||
+      !float_field_ok(L.a_grav_mesh, 3, L.stride) || L.time_bin < 8 || L.time_bin >= L.stride ||
       L.type < 8 || L.type >= L.stride) {
     set_error("the link needs id_or_neg_offset at byte 0 and x, v_full, a_grav, a_grav_mesh, "
               "time_bin and type inside the gpart record of %d bytes, aligned to their type",
@@ -178,12 +170,7 @@ void couple_release(swh_space* s) {
   s->link_cnt.release();
   if (s->link_event) (void)hipEventDestroy(s->link_event);
   s->link_event = nullptr;
-  for (auto& pair : s->link_tev)
-    for (auto& e : pair)
-      if (e) {
-        (void)hipEventDestroy(e);
-        e = nullptr;
-      }
+  s->link_timer.release();
 }
 
 void couple_release(swh_gspace* g) {
@@ -192,17 +179,16 @@ void couple_release(swh_gspace* g) {
   g->link_event = nullptr;
 }
 
-swh_status couple_stage_begin(swh_space* s, int stage, hipStream_t st) {
-  for (auto& e : s->link_tev[stage])
-    if (!e) SWH_HIP(hipEventCreate(&e));
-  SWH_HIP(hipEventRecord(s->link_tev[stage][0], st));
-  return SWH_OK;
+swh_status need_link(const swh_space* s, const char* what) {
+  if (s->link) return SWH_OK;
+  set_error("swh_space_link_gspace must precede %s", what);
+  return SWH_ERR_STATE;
 }
 
-swh_status couple_stage_end(swh_space* s, int stage, hipStream_t st) {
-  SWH_HIP(hipEventRecord(s->link_tev[stage][1], st));
-  s->link_timed[stage] = true;
-  return SWH_OK;
+swh_status need_pull(const swh_space* s, const char* what) {
+  if (s->gp_pulled) return SWH_OK;
+  set_error("%s: no swh_space_pull_gravity since the last rebuild or upload", what);
+  return SWH_ERR_STATE;
 }
 
 // `second` waits (on the device) for what is queued on `first` now.
@@ -214,10 +200,7 @@ static swh_status order_streams(hipEvent_t* ev, hipStream_t first, hipStream_t s
 }
 
 static swh_status linked(swh_space* s, const char* what) {
-  if (!s->link) {
-    set_error("swh_space_link_gspace must precede %s", what);
-    return SWH_ERR_STATE;
-  }
+  SWH_TRY(need_link(s, what));
   if (!s->built) {
     set_error("swh_space_rebuild must precede %s", what);
     return SWH_ERR_STATE;
@@ -323,12 +306,12 @@ swh_status swh_space_pull_gravity(swh_space* s) {
   SWH_TRY(couple_layout(g, &L));
   SWH_HIP(hipSetDevice(s->ctx->device));
   SWH_TRY(order_streams(&g->link_event, g->stream, s->stream));
-  SWH_TRY(couple_stage_begin(s, LT_PULL, s->stream));
+  SWH_TRY(s->link_timer.begin(LT_PULL, s->stream));
   hipLaunchKernelGGL(pull_kernel, dim3(couple_grid(g->n)), dim3(256), 0, s->stream, L,
                      g->aos.as<const char>(), g->n, s->n, s->iperm.as<const int>(),
                      s->gp_agrav_s.as<float4>(), s->gp_amesh_s.as<float4>());
   SWH_HIP(hipGetLastError());
-  SWH_TRY(couple_stage_end(s, LT_PULL, s->stream));
+  SWH_TRY(s->link_timer.end(LT_PULL, s->stream));
   s->gp_pulled = true;
   // the gspace's later work (a tree build moves the records) waits for the read
   return order_streams(&s->link_event, s->stream, g->stream);
@@ -353,14 +336,14 @@ swh_status swh_space_push_gparts(swh_space* s, const swh_push_params* Q) {
   SWH_HIP(hipSetDevice(s->ctx->device));
   if (Q->what & SWH_PUSH_V_FULL) SWH_TRY(space_ensure_xsorted(s));
   SWH_TRY(order_streams(&s->link_event, s->stream, g->stream));
-  SWH_TRY(couple_stage_begin(s, LT_PUSH, g->stream));
+  SWH_TRY(s->link_timer.begin(LT_PUSH, g->stream));
   hipLaunchKernelGGL(push_kernel, dim3(couple_grid(g->n)), dim3(256), 0, g->stream, L,
                      g->aos.as<char>(), g->n, s->n, s->iperm.as<const int>(),
                      s->pos.as<const double4>(), s->vfull_s.as<const float4>(),
                      s->tb.as<const int8_t>(), Q->what, Q->periodic, Q->dim[0], Q->dim[1],
                      Q->dim[2]);
   SWH_HIP(hipGetLastError());
-  SWH_TRY(couple_stage_end(s, LT_PUSH, g->stream));
+  SWH_TRY(s->link_timer.end(LT_PUSH, g->stream));
   if (Q->what & SWH_PUSH_X) {  // as swh_gspace_drift: the cells no longer bound their gparts
     g->mpoles_valid = false;
     g->tree_stale = true;
@@ -372,13 +355,7 @@ swh_status swh_space_push_gparts(swh_space* s, const swh_push_params* Q) {
 swh_status swh_space_link_times(swh_space* s, float* ms) {
   if (!s || !ms) return SWH_ERR_ARG;
   SWH_HIP(hipSetDevice(s->ctx->device));
-  for (int k = 0; k < 3; k++) {
-    ms[k] = -1.f;
-    if (!s->link_timed[k]) continue;
-    SWH_HIP(hipEventSynchronize(s->link_tev[k][1]));
-    SWH_HIP(hipEventElapsedTime(&ms[k], s->link_tev[k][0], s->link_tev[k][1]));
-  }
-  return SWH_OK;
+  return s->link_timer.read(ms);
 }
 
 }  // extern "C"

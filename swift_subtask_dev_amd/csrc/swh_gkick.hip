@@ -13,8 +13,8 @@
 // The kick / timestep kernel is one template <K2, TS, K1>, as swh_kick.hip's
 // step_kernel: the fused launch and the three separate ones run the same
 // per-gpart functions and hand their results on through float / int8 values
-// either way, so both routes give the same bits. Its record is reduced per
-// wave, per block in LDS, then with one integer atomic per block and field.
+// either way, so both routes give the same bits. Its record is swh_steprec.h's,
+// with one slot per 128 bytes.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -24,20 +24,20 @@
 #include "swh_gstep.h"
 #include "swh_internal.h"
 #include "swh_physics.h"
+#include "swh_steprec.h"
 #include "swh_timeline.h"
-#include "swh_wave.h"
 
 // a * b + c stays two roundings, in every instantiation alike
 #pragma clang fp contract(off)
 
 namespace swh {
 
-constexpr int kGBinTable = SWH_NUM_TIME_BINS + 1;
+static_assert(kBinTable == SWH_NUM_TIME_BINS + 1, "the kick tables of swifthip.h");
 
 struct GKickDev {
   int max_active_bin;
   double dt_mesh;              // dt_kick_mesh_grav of this call
-  double dt_grav[kGBinTable];  // half-step per bin
+  double dt_grav[kBinTable];   // half-step per bin
 };
 
 struct GTimestepDev {
@@ -50,15 +50,6 @@ struct GStepLayout {
   int stride, x, v_full, a_grav, a_grav_mesh, potential, potential_mesh, epsilon, time_bin, type;
   int old_a_grav_norm;  // -1: not in the record
 };
-
-// record slots (u64 each, all reduced by atomicMax / atomicAdd from zero),
-// one per 128 bytes: the blocks' atomics on one slot serialise, and slots that
-// share a cache line serialise with each other too (measured at 524,288
-// gparts: the timestep's five slots in one line cost 100 us of its 138)
-constexpr int kGRecStride = 16;
-enum { GREC_END_MIN = 0, GREC_END_MAX = kGRecStride, GREC_BEG_MAX = 2 * kGRecStride,
-       GREC_UPDATED = 3 * kGRecStride, GREC_BELOW = 4 * kGRecStride, GREC_VMAX = 5 * kGRecStride,
-       GREC_SLOTS = 6 * kGRecStride };
 
 // The fields of a record from v_full on, in registers. STD: the
 // multi-softening record, bytes 32..96 as four 16-byte pieces
@@ -125,18 +116,6 @@ struct GRec {
     }
   }
 };
-
-__device__ __forceinline__ long long gwave_max_ll(long long v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const long long w = __shfl_xor(v, o);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned int gwave_sum_u(unsigned int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 template <bool STD>
 __global__ __launch_bounds__(256) void gdrift_kernel(GStepLayout L, char* __restrict__ aos,
@@ -209,14 +188,8 @@ __global__ __launch_bounds__(256) void gstep_kernel(GStepLayout L, char* __restr
                                                     int64_t n, GKickDev k2, GTimestepDev T,
                                                     GKickDev k1,
                                                     unsigned long long* __restrict__ rec) {
-  __shared__ long long sm_t[3][4];
-  __shared__ unsigned int sm_c[2][4];
-  __shared__ float sm_v[4];
-  // end_min is reduced as the max of (max_nr_timesteps - ti_end): every slot
-  // of the record starts at zero
-  long long end_min_c = 0, end_max = 0, beg_max = 0;
+  StepRecLane part;
   unsigned int n_updated = 0, n_below = 0;
-  float vmax = 0.f;
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
        s += (int64_t)gridDim.x * blockDim.x) {
     char* r = aos + s * L.stride;
@@ -228,8 +201,7 @@ __global__ __launch_bounds__(256) void gstep_kernel(GStepLayout L, char* __restr
     g.load(L, r);
     bool moved = false;
     if (K2 && bin <= k2.max_active_bin) {
-      const int b = bin < 0 ? 0 : (bin >= kGBinTable ? kGBinTable - 1 : bin);
-      kick_gpart(g.v, g.a, g.am, k2.dt_grav[b], k2.dt_mesh);
+      kick_gpart(g.v, g.a, g.am, k2.dt_grav[kick_bin(bin)], k2.dt_mesh);
       moved = true;
     }
     if (TS) {
@@ -247,86 +219,25 @@ __global__ __launch_bounds__(256) void gstep_kernel(GStepLayout L, char* __restr
         ti_end = get_integer_time_end(T.T.ti_current, bin);
         ti_beg = get_integer_time_begin(T.T.ti_current + 1, bin);
       }
-      const long long c = kMaxNrTimesteps - ti_end;
-      end_min_c = c > end_min_c ? c : end_min_c;
-      end_max = ti_end > end_max ? ti_end : end_max;
-      beg_max = ti_beg > beg_max ? ti_beg : beg_max;
+      part.add_times(ti_end, ti_beg);
     }
     if (K1 && bin <= k1.max_active_bin) {  // gpart_is_starting, on the new bin
-      const int b = bin < 0 ? 0 : (bin >= kGBinTable ? kGBinTable - 1 : bin);
-      kick_gpart(g.v, g.a, g.am, k1.dt_grav[b], k1.dt_mesh);
+      kick_gpart(g.v, g.a, g.am, k1.dt_grav[kick_bin(bin)], k1.dt_mesh);
       moved = true;
     }
     if (moved) g.store_v(L, r);
-    vmax = fmaxf(vmax, sqrtf(g.v[0] * g.v[0] + g.v[1] * g.v[1] + g.v[2] * g.v[2]));
+    part.add_speed(sqrtf(g.v[0] * g.v[0] + g.v[1] * g.v[1] + g.v[2] * g.v[2]));
   }
-  const int w = (int)(threadIdx.x >> 6);
-  const bool lead = (threadIdx.x & 63) == 0;
-  if (TS) {
-    end_min_c = gwave_max_ll(end_min_c);
-    end_max = gwave_max_ll(end_max);
-    beg_max = gwave_max_ll(beg_max);
-    n_updated = gwave_sum_u(n_updated);
-    n_below = gwave_sum_u(n_below);
-    if (lead) {
-      sm_t[0][w] = end_min_c;
-      sm_t[1][w] = end_max;
-      sm_t[2][w] = beg_max;
-      sm_c[0][w] = n_updated;
-      sm_c[1][w] = n_below;
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-  if (lead) sm_v[w] = vmax;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  if (TS) {
-    for (int k = 0; k < 3; k++) {
-      long long m = sm_t[k][0];
-      for (int j = 1; j < 4; j++) m = sm_t[k][j] > m ? sm_t[k][j] : m;
-      if (m > 0) atomicMax(rec + GREC_END_MIN + k * kGRecStride, (unsigned long long)m);
-    }
-    for (int k = 0; k < 2; k++) {
-      const unsigned int c = sm_c[k][0] + sm_c[k][1] + sm_c[k][2] + sm_c[k][3];
-      if (c) atomicAdd(rec + GREC_UPDATED + k * kGRecStride, (unsigned long long)c);
-    }
-  }
-  const float m = fmaxf(fmaxf(sm_v[0], sm_v[1]), fmaxf(sm_v[2], sm_v[3]));
-  if (m > 0.f) atomicMax(rec + GREC_VMAX, (unsigned long long)__float_as_uint(m));
+  part.commit<kRecStrideGspace, TS, false>(rec, n_updated, n_below);
 }
 
 void gstep_release(swh_gspace* g) {
-  g->gstep_rec.release();
-  g->gstep_host.release();
-  if (g->gstep_event) {
-    (void)hipEventDestroy(g->gstep_event);
-    g->gstep_event = nullptr;
-  }
-  for (auto& pair : g->gstep_tev)
-    for (auto& e : pair)
-      if (e) {
-        (void)hipEventDestroy(e);
-        e = nullptr;
-      }
+  g->gstep.release();
+  g->gstep_timer.release();
 }
 
-// The events that bracket a stage's launch (swh_gspace_step_times).
+// The stages of swh_gspace.gstep_timer (swh_gspace_step_times).
 enum { GT_DRIFT = 0, GT_INIT, GT_END_FORCE, GT_STEP };
-static swh_status stage_begin(swh_gspace* g, int stage) {
-  for (auto& e : g->gstep_tev[stage])
-    if (!e) SWH_HIP(hipEventCreate(&e));
-  SWH_HIP(hipEventRecord(g->gstep_tev[stage][0], g->stream));
-  return SWH_OK;
-}
-static swh_status stage_end(swh_gspace* g, int stage) {
-  SWH_HIP(hipEventRecord(g->gstep_tev[stage][1], g->stream));
-  g->gstep_timed[stage] = true;
-  return SWH_OK;
-}
-
-static bool float_field_ok(int off, int count, int stride) {
-  return off >= 0 && off % 4 == 0 && off + 4 * count <= stride;
-}
 
 static swh_status check_step_layout(const swh_gpart_step_layout& S, int stride) {
   if (!float_field_ok(S.off_v_full, 3, stride) || !float_field_ok(S.off_a_grav_mesh, 3, stride) ||
@@ -413,7 +324,7 @@ static int gstep_grid(int64_t n) {
 static void fill_gkick(const swh_gkick_params* K, GKickDev* d) {
   d->max_active_bin = K->max_active_bin;
   d->dt_mesh = K->dt_kick_mesh_grav;
-  for (int b = 0; b < kGBinTable; b++) {
+  for (int b = 0; b < kBinTable; b++) {
     // non-cosmological kick_get_grav_kick_dt: half a step of bin b
     const double half = (double)(get_integer_timestep(b) / 2) * K->time_base;
     d->dt_grav[b] = K->dt_kick_grav ? K->dt_kick_grav[b] : half;
@@ -429,17 +340,8 @@ static swh_status launch_gstep(swh_gspace* g, const swh_gkick_params* k2,
   if (g->n == 0) return SWH_OK;
   SWH_HIP(hipSetDevice(g->ctx->device));
   hipStream_t st = g->stream;
-  SWH_TRY(g->gstep_host.reserve(2 * GREC_SLOTS * sizeof(unsigned long long)));
-  if (!g->gstep_rec.ptr) {
-    SWH_TRY(g->gstep_rec.reserve(GREC_SLOTS * sizeof(unsigned long long)));
-    SWH_HIP(hipMemsetAsync(g->gstep_rec.ptr, 0, GREC_SLOTS * sizeof(unsigned long long), st));
-  }
-  if (!g->gstep_event) SWH_HIP(hipEventCreateWithFlags(&g->gstep_event, hipEventDisableTiming));
-  unsigned long long* rec = g->gstep_rec.as<unsigned long long>();
-  // the timestep's fields stay until the next timestep; every launch measures
-  // max |v_full| anew
-  if (TS) SWH_HIP(hipMemsetAsync(rec, 0, GREC_VMAX * sizeof(unsigned long long), st));
-  SWH_HIP(hipMemsetAsync(rec + GREC_VMAX, 0, sizeof(unsigned long long), st));
+  SWH_TRY(g->gstep.prepare(st, TS));
+  unsigned long long* rec = g->gstep.dev();
   static const swh_gkick_params kNoKick{};
   GKickDev d2, d1;
   GTimestepDev dt{};
@@ -459,7 +361,7 @@ static swh_status launch_gstep(swh_gspace* g, const swh_gkick_params* k2,
   }
   const GStepLayout L = step_layout_of(g);
   const int grid = gstep_grid(g->n);
-  SWH_TRY(stage_begin(g, GT_STEP));
+  SWH_TRY(g->gstep_timer.begin(GT_STEP, st));
   if (is_std_layout(L, g->aos.ptr))
     hipLaunchKernelGGL((gstep_kernel<K2, TS, K1, true>), dim3(grid), dim3(256), 0, st, L,
                        g->aos.as<char>(), g->n, d2, dt, d1, rec);
@@ -467,16 +369,9 @@ static swh_status launch_gstep(swh_gspace* g, const swh_gkick_params* k2,
     hipLaunchKernelGGL((gstep_kernel<K2, TS, K1, false>), dim3(grid), dim3(256), 0, st, L,
                        g->aos.as<char>(), g->n, d2, dt, d1, rec);
   SWH_HIP(hipGetLastError());
-  SWH_TRY(stage_end(g, GT_STEP));
-  SWH_HIP(hipMemcpyAsync(g->gstep_host.ptr, rec, GREC_SLOTS * sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost, st));
-  SWH_HIP(hipEventRecord(g->gstep_event, st));
-  g->gstep_pending = true;
-  if (TS) {
-    g->gstep_has_ts = true;
-    // host-only note next to the record: the dt_min of step_result's message
-    static_cast<double*>(g->gstep_host.ptr)[GREC_SLOTS] = T->dt_min;
-  }
+  SWH_TRY(g->gstep_timer.end(GT_STEP, st));
+  SWH_TRY(g->gstep.readback(st));
+  if (TS) g->gstep.note_timestep(T->dt_min);
   return SWH_OK;
 }
 
@@ -508,7 +403,7 @@ swh_status swh_gspace_drift(swh_gspace* g, const swh_gdrift_params* D) {
   SWH_HIP(hipSetDevice(g->ctx->device));
   const GStepLayout L = step_layout_of(g);
   const int grid = gstep_grid(g->n);
-  SWH_TRY(stage_begin(g, GT_DRIFT));
+  SWH_TRY(g->gstep_timer.begin(GT_DRIFT, g->stream));
   if (is_std_layout(L, g->aos.ptr))
     hipLaunchKernelGGL(gdrift_kernel<true>, dim3(grid), dim3(256), 0, g->stream, L,
                        g->aos.as<char>(), g->n, D->dt_drift, D->periodic, D->dim[0], D->dim[1],
@@ -518,7 +413,7 @@ swh_status swh_gspace_drift(swh_gspace* g, const swh_gdrift_params* D) {
                        g->aos.as<char>(), g->n, D->dt_drift, D->periodic, D->dim[0], D->dim[1],
                        D->dim[2]);
   SWH_HIP(hipGetLastError());
-  SWH_TRY(stage_end(g, GT_DRIFT));
+  SWH_TRY(g->gstep_timer.end(GT_DRIFT, g->stream));
   // the cells' geometry no longer bounds their gparts
   g->mpoles_valid = false;
   g->tree_stale = true;
@@ -532,7 +427,7 @@ swh_status swh_gspace_init_grav(swh_gspace* g, int32_t max_active_bin) {
   SWH_HIP(hipSetDevice(g->ctx->device));
   const GStepLayout L = step_layout_of(g);
   const int grid = gstep_grid(g->n);
-  SWH_TRY(stage_begin(g, GT_INIT));
+  SWH_TRY(g->gstep_timer.begin(GT_INIT, g->stream));
   if (is_std_layout(L, g->aos.ptr))
     hipLaunchKernelGGL(ginit_kernel<true>, dim3(grid), dim3(256), 0, g->stream, L,
                        g->aos.as<char>(), g->n, max_active_bin, g->accel.as<double4>());
@@ -540,7 +435,7 @@ swh_status swh_gspace_init_grav(swh_gspace* g, int32_t max_active_bin) {
     hipLaunchKernelGGL(ginit_kernel<false>, dim3(grid), dim3(256), 0, g->stream, L,
                        g->aos.as<char>(), g->n, max_active_bin, g->accel.as<double4>());
   SWH_HIP(hipGetLastError());
-  return stage_end(g, GT_INIT);
+  return g->gstep_timer.end(GT_INIT, g->stream);
 }
 
 swh_status swh_gspace_end_force(swh_gspace* g, const swh_gend_params* E) {
@@ -550,7 +445,7 @@ swh_status swh_gspace_end_force(swh_gspace* g, const swh_gend_params* E) {
   SWH_HIP(hipSetDevice(g->ctx->device));
   const GStepLayout L = step_layout_of(g);
   const int grid = gstep_grid(g->n);
-  SWH_TRY(stage_begin(g, GT_END_FORCE));
+  SWH_TRY(g->gstep_timer.begin(GT_END_FORCE, g->stream));
   if (is_std_layout(L, g->aos.ptr))
     hipLaunchKernelGGL(gend_kernel<true>, dim3(grid), dim3(256), 0, g->stream, L,
                        g->aos.as<char>(), g->n, g->active.as<const int8_t>(),
@@ -562,7 +457,7 @@ swh_status swh_gspace_end_force(swh_gspace* g, const swh_gend_params* E) {
                        g->accel.as<double4>(), E->const_G, E->potential_normalisation,
                        E->periodic);
   SWH_HIP(hipGetLastError());
-  return stage_end(g, GT_END_FORCE);
+  return g->gstep_timer.end(GT_END_FORCE, g->stream);
 }
 
 swh_status swh_gspace_kick1(swh_gspace* g, const swh_gkick_params* K) {
@@ -589,43 +484,19 @@ swh_status swh_gspace_step_result(swh_gspace* g, swh_step_result* out) {
     *out = swh_step_result{kMaxNrTimesteps, 0, 0, 0, 0, 0.f, 0};
     return SWH_OK;
   }
-  if (!g->gstep_has_ts) {
+  if (!g->gstep.has_ts) {
     set_error("swh_gspace_timestep or swh_gspace_end_step must precede swh_gspace_step_result");
     return SWH_ERR_STATE;
   }
   SWH_HIP(hipSetDevice(g->ctx->device));
-  if (g->gstep_pending) {
-    SWH_HIP(hipEventSynchronize(g->gstep_event));
-    g->gstep_pending = false;
-  }
-  const unsigned long long* h = static_cast<const unsigned long long*>(g->gstep_host.ptr);
-  const unsigned int vb = (unsigned int)h[GREC_VMAX];
-  std::memcpy(&g->gstep_vmax, &vb, sizeof(vb));
-  out->ti_end_min = kMaxNrTimesteps - (int64_t)h[GREC_END_MIN];
-  out->ti_end_max = (int64_t)h[GREC_END_MAX];
-  out->ti_beg_max = (int64_t)h[GREC_BEG_MAX];
-  out->n_updated = (int64_t)h[GREC_UPDATED];
-  out->n_below_dt_min = (int64_t)h[GREC_BELOW];
-  out->vfull_max = g->gstep_vmax;
-  out->reserved = 0;
-  if (out->n_below_dt_min > 0) {
-    set_error("%lld gparts want a time-step below dt_min (%e)", (long long)out->n_below_dt_min,
-              static_cast<const double*>(g->gstep_host.ptr)[GREC_SLOTS]);
-    return SWH_ERR_ARG;
-  }
-  return SWH_OK;
+  SWH_TRY(g->gstep.fetch());
+  return g->gstep.decode(out, "gparts");
 }
 
 swh_status swh_gspace_step_times(swh_gspace* g, float* ms) {
   if (!g || !ms) return SWH_ERR_ARG;
   SWH_HIP(hipSetDevice(g->ctx->device));
-  for (int k = 0; k < 4; k++) {
-    ms[k] = -1.f;
-    if (!g->gstep_timed[k]) continue;
-    SWH_HIP(hipEventSynchronize(g->gstep_tev[k][1]));
-    SWH_HIP(hipEventElapsedTime(&ms[k], g->gstep_tev[k][0], g->gstep_tev[k][1]));
-  }
-  return SWH_OK;
+  return g->gstep_timer.read(ms);
 }
 
 }  // extern "C"

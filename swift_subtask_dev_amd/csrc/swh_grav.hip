@@ -31,6 +31,7 @@
 #include "swh_internal.h"
 #include "swh_mpole.h"
 #include "swh_physics.h"
+#include "swh_steprec.h"
 #include "swh_wave.h"
 
 namespace swh {
@@ -348,11 +349,6 @@ __device__ __forceinline__ void p2p_tile(const double* sx, const double* sy, con
   }
 }
 
-// Largest value over a wave (lanes without one pass 0).
-__device__ __forceinline__ double wave_max_f64(double v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
 
 // Per pair: which of this thread's i-particles take the source leaf's
 // multipole instead (allow_mpole pairs only; block-uniform branch).
@@ -442,7 +438,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(MPOLE ? 3 :
           sh[threadIdx.x] = g.hinv[gj];
           sm[threadIdx.x] = g.mass[gj];
         }
-        e2 = wave_max_f64(e2);
+        e2 = wave_max_d(e2);
         if ((threadIdx.x & 63) == 0) swmax[threadIdx.x / 64] = e2;
         __syncthreads();
         double tmax = swmax[0];
@@ -505,7 +501,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(MPOLE ? 3 :
     }
   }
   if (counter) {
-    for (int o = 32; o > 0; o >>= 1) nint += __shfl_xor(nint, o);
+    nint = wave_sum_ull(nint);
     if ((threadIdx.x & 63) == 0 && nint) atomicAdd(counter, nint);
   }
 }
@@ -668,7 +664,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void p2
       const double4 q = g.pos[gi];
       e = fmax(fabs(q.x - cx), fmax(fabs(q.y - cy), fabs(q.z - cz)));
     }
-    e = wave_max_f64(e);
+    e = wave_max_d(e);
     lim_x = 0.5 * dimx * (1. - 1e-12) - e;
     lim_y = 0.5 * dimy * (1. - 1e-12) - e;
     lim_z = 0.5 * dimz * (1. - 1e-12) - e;
@@ -800,7 +796,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void p2
       // (the reduction outside the act test: every lane staged gparts, also
       // the lanes past the leaf's count or of an inactive i, and a shuffle
       // reads nothing from a lane that does not execute it)
-      const double tile_e2 = wave_max_f64(e2max);
+      const double tile_e2 = wave_max_d(e2max);
       const double emax = act ? fmax(hi2, tile_e2) : 0.;
       const bool wrap = periodic && __any(far);
       wave_sync();
@@ -859,7 +855,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void p2
   }
   if (counter) {
     unsigned long long n = nint;
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+    n = wave_sum_ull(n);
     if (lane == 0 && n) atomicAdd(counter, n);
   }
 }
@@ -954,7 +950,7 @@ __global__ __launch_bounds__(kGravBlock) void p2p_kernel_f32(
     }
   }
   if (counter) {
-    for (int o = 32; o > 0; o >>= 1) nint += __shfl_xor(nint, o);
+    nint = wave_sum_ull(nint);
     if ((threadIdx.x & 63) == 0 && nint) atomicAdd(counter, nint);
   }
 }
@@ -997,7 +993,7 @@ __global__ __launch_bounds__(64) void pp_trunc_count_kernel(
         n += (unsigned long long)(J.count - ((gi >= J.start && gi < J.start + J.count) ? 1 : 0));
     }
   }
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  n = wave_sum_ull(n);
   if (lane == 0 && n) atomicAdd(counter, n);
 }
 
@@ -1306,7 +1302,7 @@ __global__ __launch_bounds__(kGravBlock) __attribute__((amdgpu_waves_per_eu(SMAL
     }
   }
   if (counter) {
-    for (int o = 32; o > 0; o >>= 1) nm += __shfl_xor(nm, o);
+    nm = wave_sum_ull(nm);
     if ((threadIdx.x & 63) == 0 && nm) atomicAdd(counter + 1, nm);
   }
 }
@@ -1394,8 +1390,7 @@ swh_status swh_gspace_upload(swh_gspace* g, const void* gparts, int64_t count,
   g->order_valid = false;  // swh_gspace_tree_order: the records are in upload order
   g->tree_stale = false;   // a drift's staleness went with the records it moved
   g->step_checked = false;
-  g->gstep_has_ts = false;
-  g->gstep_pending = false;
+  g->gstep.invalidate();
   if (count == 0) return SWH_OK;
   SWH_TRY(g->aos.reserve((size_t)count * L.stride));
   SWH_TRY(g->pos.reserve((size_t)count * sizeof(double4)));

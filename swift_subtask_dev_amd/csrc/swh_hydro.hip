@@ -30,7 +30,7 @@ __global__ __launch_bounds__(kCounterStripes) void stripe_reduce_kernel(
     if (k == 1 || k == 2) continue;  // slots 1-2 hold other state (swh_hydro.hip counter map)
     unsigned long long v = stripes[t * 8 + k];
     stripes[t * 8 + k] = 0ull;
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum_ull(v);
     if ((t & 63) == 0 && v) atomicAdd(out + k, v);
   }
 }
@@ -397,7 +397,7 @@ void walk_subset_kernel(GridDev g, SoA a, ListDev ld,
   if (act && s == 0) st.store(a, i);
   if (counter) {
     unsigned long long v = (unsigned long long)((act && s == 0) ? st.n : 0);
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum_ull(v);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(counter_stripe(counter), v);
   }
 }
@@ -619,7 +619,7 @@ __global__ __launch_bounds__(1024) void ghost_kernel(
   // h max: an atomic only when it changes something (all blocks hitting one
   // address serialise at ~10 ns per atomic)
   float m = hf;
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+  m = wave_max_f(m);
   if ((threadIdx.x & 63) == 0 && m > 0.f) atomic_max_bits_if(hmax_bits, __float_as_uint(m));
 }
 

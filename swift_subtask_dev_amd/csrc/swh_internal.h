@@ -91,6 +91,73 @@ struct HostBuf {
   }
 };
 
+// The step record of a space or a gspace, host side: the u64 slots a time step
+// reduces into on the device, their pinned copy and the event behind the last
+// copy. swh_steprec.h has the slots, the kernels' side and these methods.
+constexpr int kRecStrideSpace = 1;    // u64 from one slot to the next: packed,
+constexpr int kRecStrideGspace = 16;  // one slot per 128 bytes
+struct StepRecord {
+  int stride;
+  DevBuf rec;
+  HostBuf host;
+  hipEvent_t event = nullptr;  // behind the last record copy
+  bool pending = false;        // a record copy is queued and not yet read
+  bool has_ts = false;         // the record holds a timestep's fields
+  double dt_min = 0.;          // of that timestep (decode's message)
+  float vmax = 0.f;            // max |v_full| of the last fetched record
+  explicit StepRecord(int stride_) : stride(stride_) {}
+  unsigned long long* dev() const { return rec.as<unsigned long long>(); }
+  // before a launch: the buffers and the event; the timestep's fields stay
+  // until the next timestep (ts), every launch measures max |v_full| anew
+  swh_status prepare(hipStream_t st, bool ts);
+  swh_status readback(hipStream_t st);  // after it: queue the copy to the host
+  void note_timestep(double dt_min_) {
+    has_ts = true;
+    dt_min = dt_min_;
+  }
+  swh_status fetch();  // wait for a queued copy; vmax
+  // the fetched record; noun: what the record counts ("parts", "gparts")
+  swh_status decode(swh_step_result* out, const char* noun) const;
+  void invalidate() { pending = has_ts = false; }
+  void release();
+};
+
+// HIP events around the last launch of each of N stages.
+template <int N>
+struct StageTimer {
+  hipEvent_t ev[N][2] = {};
+  bool timed[N] = {};
+  swh_status begin(int k, hipStream_t st) {
+    for (auto& e : ev[k])
+      if (!e) SWH_HIP(hipEventCreate(&e));
+    SWH_HIP(hipEventRecord(ev[k][0], st));
+    return SWH_OK;
+  }
+  swh_status end(int k, hipStream_t st) {
+    SWH_HIP(hipEventRecord(ev[k][1], st));
+    timed[k] = true;
+    return SWH_OK;
+  }
+  // ms[k]: the last launch of stage k, -1 if it never ran; waits for it
+  swh_status read(float* ms) {
+    for (int k = 0; k < N; k++) {
+      ms[k] = -1.f;
+      if (!timed[k]) continue;
+      SWH_HIP(hipEventSynchronize(ev[k][1]));
+      SWH_HIP(hipEventElapsedTime(&ms[k], ev[k][0], ev[k][1]));
+    }
+    return SWH_OK;
+  }
+  void release() {
+    for (auto& pair : ev)
+      for (auto& e : pair)
+        if (e) {
+          (void)hipEventDestroy(e);
+          e = nullptr;
+        }
+  }
+};
+
 // Device copy of the AoS layout (offsets), passed by value to kernels.
 struct Layout {
   int stride;
@@ -109,6 +176,10 @@ struct GLayout {
   int old_a_grav_norm;  // -1: not in the record (the adaptive MAC then sees 0)
 };
 swh_status make_glayout(const swh_gpart_layout* L, GLayout* out);
+// `count` floats at byte `off` of a record lie inside its stride, 4-byte aligned
+inline bool float_field_ok(int off, int count, int stride) {
+  return off >= 0 && off % 4 == 0 && off + 4 * count <= stride;
+}
 
 // Per-task worker: one stream + staging buffers, leased per host thread.
 struct TaskWorker {
@@ -193,11 +264,7 @@ struct swh_space {
   // authoritative ones: the kicks write them, and a rebuild scatters them back
   // to caller order before the sort order changes (space_xparts_to_caller).
   bool has_ufull = false;     // the uploaded xparts carried u_full
-  swh::DevBuf step_rec;       // u64[8]: the record the step kernel reduces into
-  swh::HostBuf step_host;     // pinned: u64[0..8) record read back, [8..16) its initial values
-  hipEvent_t step_event = nullptr;  // behind the last record copy
-  bool step_pending = false;  // a record copy is queued and not yet read (vfull_max)
-  bool step_has_ts = false;   // the record holds a timestep's fields
+  swh::StepRecord step{swh::kRecStrideSpace};  // the record the step kernel reduces into
   // time-step limiter (swh_limiter.hip): the wake-up word of every particle
   // (i32, the reference's int8 limiter_data.wakeup widened for the integer
   // atomic max of the neighbour loop), authoritative in sorted order
@@ -209,6 +276,9 @@ struct swh_space {
   swh::HostBuf lim_host;
   hipEvent_t lim_event = nullptr;
   bool lim_has = false;
+  // a limiter loop ran since the last apply: only the loop sets wake-ups and
+  // the apply resets them all, so an apply without one has nothing to do
+  bool wake_dirty = false;
   // gas <-> gpart link (swh_couple.hip): the gspace whose gas gparts name this
   // space's parts, their a_grav and a_grav_mesh in sorted order (float4, filled
   // by swh_space_pull_gravity, void after a rebuild), the check's scratch
@@ -218,10 +288,8 @@ struct swh_space {
   bool gp_pulled = false;
   swh::DevBuf link_mark, link_cnt;  // i32[n] parts named, u32[4] the check's counts
   hipEvent_t link_event = nullptr;  // recorded on this space's stream for the gspace's
-  // HIP events around the last pull, push and linked kick / timestep launch
-  // (swh_space_link_times)
-  hipEvent_t link_tev[3][2] = {};
-  bool link_timed[3] = {false, false, false};
+  // the last pull, push and linked kick / timestep launch (swh_space_link_times)
+  swh::StageTimer<3> link_timer;
   // grid
   swh::DevBuf cell_start;  // int32[ncell+1], indexed by Morton rank
   swh::DevBuf cell_rank;   // int32[ncell]: linear cell -> Morton rank
@@ -338,16 +406,9 @@ struct swh_gspace {
   bool step_layout_set = false;
   bool step_checked = false;   // every offset the step kernels use lies inside the stride
   bool tree_stale = false;     // drifted since the tree was installed (swh_gspace_drift)
-  swh::DevBuf gstep_rec;       // u64 slots, 128 bytes apart
-  swh::HostBuf gstep_host;     // the record read back, then the timestep's dt_min
-  hipEvent_t gstep_event = nullptr;  // behind the last record copy
-  bool gstep_pending = false;  // a record copy is queued and not yet read
-  bool gstep_has_ts = false;   // the record holds a timestep's fields
-  float gstep_vmax = 0.f;      // max |v_full| of the last fetched record
-  // HIP events around the last launch of each stage: drift, init_grav,
-  // end_force, kick / timestep / end_step (swh_gspace_step_times)
-  hipEvent_t gstep_tev[4][2] = {};
-  bool gstep_timed[4] = {false, false, false, false};
+  swh::StepRecord gstep{swh::kRecStrideGspace};
+  // drift, init_grav, end_force, kick / timestep / end_step (swh_gspace_step_times)
+  swh::StageTimer<4> gstep_timer;
   // gas <-> gpart link (swh_couple.hip)
   swh_space* link = nullptr;
   hipEvent_t link_event = nullptr;  // recorded on this gspace's stream for the space's
@@ -356,7 +417,7 @@ struct swh_gspace {
 namespace swh {
 void mesh_release(swh_gspace* g);  // swh_mesh.hip: mesh buffers and hipFFT plans
 void gtree_release(swh_gspace* g);  // swh_gtree.hip: the tree build's scratch and events
-void gstep_release(swh_gspace* g);  // swh_gkick.hip: the step record's buffers and event
+void gstep_release(swh_gspace* g);  // swh_gkick.hip: the step record and the stage timer
 // swh_grav.hip: the bookkeeping of a cell table, shared by swh_gspace_set_tree
 // and swh_gspace_build_tree. device_built: the table is already in tree_d and
 // leaf_of is filled on the device (gtree_fill_leaf_of), nothing O(N) on the host.
@@ -368,7 +429,9 @@ void couple_unlink(swh_space* s);
 void couple_unlink(swh_gspace* g);
 void couple_release(swh_space* s);
 void couple_release(swh_gspace* g);
-enum { LT_PULL = 0, LT_PUSH, LT_STEP };
-swh_status couple_stage_begin(swh_space* s, int stage, hipStream_t st);
-swh_status couple_stage_end(swh_space* s, int stage, hipStream_t st);
+enum { LT_PULL = 0, LT_PUSH, LT_STEP };  // the stages of swh_space.link_timer
+// what the entries of a linked space ask: a link, and (past the empty space)
+// this step's gravity pulled
+swh_status need_link(const swh_space* s, const char* what);
+swh_status need_pull(const swh_space* s, const char* what);
 }

@@ -9,9 +9,7 @@
 // float / int8 values either way (registers when fused, the SoA when not), so
 // both routes give the same bits. The kernel streams the sorted SoA and the
 // sorted xpart copies (v_full with u_full in its w lane, a_grav, the gpart
-// flag) once, grid-stride, and reduces the step's record per wave, then per
-// block in LDS, then with one integer atomic per block and field: the record
-// does not depend on the order of the blocks.
+// flag) once, grid-stride, and reduces the step's record (swh_steprec.h).
 // A fourth flag, LK, is the same kernel for a space linked to a gspace
 // (swh_couple.hip): a linked particle's gravity comes from the two arrays
 // swh_space_pull_gravity filled (its gpart's a_grav and a_grav_mesh), with the
@@ -25,8 +23,8 @@
 #include "swh_internal.h"
 #include "swh_physics.h"
 #include "swh_space.h"
+#include "swh_steprec.h"
 #include "swh_timeline.h"
-#include "swh_wave.h"
 
 // a * b + c stays two roundings, as the gcc-built reference evaluates it, in
 // every instantiation alike
@@ -34,7 +32,7 @@
 
 namespace swh {
 
-constexpr int kBinTable = SWH_NUM_TIME_BINS + 1;
+static_assert(kBinTable == SWH_NUM_TIME_BINS + 1, "the kick tables of swifthip.h");
 
 struct KickDev {
   int max_active_bin;
@@ -51,13 +49,6 @@ struct TimestepDev {
   double a_factor_grav_accel, a_factor_hydro_accel;
   int64_t ti_current;
 };
-
-// (the record slots REC_*: swh_space.h)
-
-// the row of the per-bin half-step tables for time bin `bin`
-__device__ __forceinline__ int kick_bin(int bin) {
-  return bin < 0 ? 0 : (bin >= kBinTable ? kBinTable - 1 : bin);
-}
 
 // SPHENIX hydro_kick_extra (hydro.h:1103-1130): u_full, and u_dt = 0 at the
 // energy floor
@@ -140,18 +131,6 @@ __device__ __forceinline__ float part_timestep(const TimestepDev& T, float h, fl
   return new_dt;
 }
 
-__device__ __forceinline__ long long wave_max_ll(long long v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const long long w = __shfl_xor(v, o);
-    v = w > v ? w : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned int wave_sum_u(unsigned int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // The link's arrays (LK): the gparts' a_grav and a_grav_mesh (sorted, pulled),
 // xp->a_grav for kick1 to write, the mesh kicks of this call.
 struct LinkDev {
@@ -170,14 +149,8 @@ __global__ __launch_bounds__(256) void step_kernel(SoA a, float4* __restrict__ v
                                                    KickDev k2, TimestepDev T, KickDev k1,
                                                    unsigned long long* __restrict__ rec,
                                                    LinkDev lk) {
-  __shared__ long long sm_t[3][4];
-  __shared__ unsigned int sm_c[2][4];
-  __shared__ float sm_v[4];
-  // end_min is reduced as the max of (max_nr_timesteps - ti_end): every slot
-  // of the record starts at zero
-  long long end_min_c = 0, end_max = 0, beg_max = 0;
+  StepRecLane part;
   unsigned int n_updated = 0, n_below = 0;
-  float vmax = 0.f;
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
        s += (int64_t)gridDim.x * blockDim.x) {
     int bin = a.tb[s];
@@ -239,10 +212,7 @@ __global__ __launch_bounds__(256) void step_kernel(SoA a, float4* __restrict__ v
           ti_end = get_integer_time_end(T.ti_current, bin);
           ti_beg = get_integer_time_begin(T.ti_current + 1, bin);
         }
-        const long long c = kMaxNrTimesteps - ti_end;
-        end_min_c = c > end_min_c ? c : end_min_c;
-        end_max = ti_end > end_max ? ti_end : end_max;
-        beg_max = ti_beg > beg_max ? ti_beg : beg_max;
+        part.add_times(ti_end, ti_beg);
       }
       if (K1 && bin <= k1.max_active_bin) {  // part_is_starting, on the new bin
         if (LK && hg) {
@@ -262,41 +232,9 @@ __global__ __launch_bounds__(256) void step_kernel(SoA a, float4* __restrict__ v
         if (ac.w != u_dt_in) a.acc[s] = ac;  // u_dt = 0 at the energy floor
       }
     }
-    vmax = fmaxf(vmax, sqrtf(vf.x * vf.x + vf.y * vf.y + vf.z * vf.z));
+    part.add_speed(sqrtf(vf.x * vf.x + vf.y * vf.y + vf.z * vf.z));
   }
-  const int w = (int)(threadIdx.x >> 6);
-  const bool lead = (threadIdx.x & 63) == 0;
-  if (TS) {
-    end_min_c = wave_max_ll(end_min_c);
-    end_max = wave_max_ll(end_max);
-    beg_max = wave_max_ll(beg_max);
-    n_updated = wave_sum_u(n_updated);
-    n_below = wave_sum_u(n_below);
-    if (lead) {
-      sm_t[0][w] = end_min_c;
-      sm_t[1][w] = end_max;
-      sm_t[2][w] = beg_max;
-      sm_c[0][w] = n_updated;
-      sm_c[1][w] = n_below;
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-  if (lead) sm_v[w] = vmax;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  if (TS) {
-    for (int k = 0; k < 3; k++) {
-      long long m = sm_t[k][0];
-      for (int j = 1; j < 4; j++) m = sm_t[k][j] > m ? sm_t[k][j] : m;
-      if (m > 0) atomicMax(rec + REC_END_MIN + k, (unsigned long long)m);
-    }
-    for (int k = 0; k < 2; k++) {
-      const unsigned int c = sm_c[k][0] + sm_c[k][1] + sm_c[k][2] + sm_c[k][3];
-      if (c) atomicAdd(rec + REC_UPDATED + k, (unsigned long long)c);
-    }
-  }
-  const float m = fmaxf(fmaxf(sm_v[0], sm_v[1]), fmaxf(sm_v[2], sm_v[3]));
-  if (m > 0.f) atomicMax(rec + REC_VMAX, (unsigned long long)__float_as_uint(m));
+  part.commit<kRecStrideSpace, TS, false>(rec, n_updated, n_below);
 }
 
 // a_grav (n x 3 floats, caller order) -> the caller-order float4 copy
@@ -356,7 +294,7 @@ static void fill_timestep(const swh_timestep_params* T, const swh_hydro_params* 
   d->ti_current = T->ti_current;
 }
 
-static swh_status step_ready(swh_space* s, const char* what) {
+swh_status step_ready(swh_space* s, const char* what) {
   if (!s->xparts_valid) {
     set_error("swh_space_upload_xparts must precede %s", what);
     return SWH_ERR_STATE;
@@ -378,30 +316,14 @@ static swh_status launch_step(swh_space* s, const swh_kick_params* k2,
                               const swh_hydro_params* P, const char* what, double dt_mesh2 = 0.,
                               double dt_mesh1 = 0., bool keep_lists = false) {
   if (!s || !P || (K2 && !k2) || (TS && !T) || (K1 && !k1)) return SWH_ERR_ARG;
-  if (LK && !s->link) {
-    set_error("swh_space_link_gspace must precede %s", what);
-    return SWH_ERR_STATE;
-  }
+  if (LK) SWH_TRY(need_link(s, what));
   if (s->n == 0) return SWH_OK;
   SWH_TRY(step_ready(s, what));
-  if (LK && !s->gp_pulled) {
-    set_error("%s: no swh_space_pull_gravity since the last rebuild or upload", what);
-    return SWH_ERR_STATE;
-  }
+  if (LK) SWH_TRY(need_pull(s, what));
   SWH_HIP(hipSetDevice(s->ctx->device));
   hipStream_t st = s->stream;
   SWH_TRY(space_ensure_xsorted(s));
-  SWH_TRY(s->step_host.reserve(2 * REC_SLOTS * sizeof(unsigned long long)));
-  if (!s->step_rec.ptr) {
-    SWH_TRY(s->step_rec.reserve(REC_SLOTS * sizeof(unsigned long long)));
-    SWH_HIP(hipMemsetAsync(s->step_rec.ptr, 0, REC_SLOTS * sizeof(unsigned long long), st));
-  }
-  if (!s->step_event) SWH_HIP(hipEventCreateWithFlags(&s->step_event, hipEventDisableTiming));
-  unsigned long long* rec = s->step_rec.as<unsigned long long>();
-  // the timestep's fields stay until the next timestep; every launch measures
-  // max |v_full| anew
-  if (TS) SWH_HIP(hipMemsetAsync(rec, 0, REC_VMAX * sizeof(unsigned long long), st));
-  SWH_HIP(hipMemsetAsync(rec + REC_VMAX, 0, sizeof(unsigned long long), st));
+  SWH_TRY(s->step.prepare(st, TS));
   static const swh_kick_params kNoKick{};
   KickDev d2, d1;
   TimestepDev dt{};
@@ -415,20 +337,15 @@ static swh_status launch_step(swh_space* s, const swh_kick_params* k2,
     lk.gp_amesh = s->gp_amesh_s.as<const float4>();
     lk.xp_agrav = s->agrav_s.as<float4>();
   }
-  if (LK) SWH_TRY(couple_stage_begin(s, LT_STEP, st));
+  if (LK) SWH_TRY(s->link_timer.begin(LT_STEP, st));
   hipLaunchKernelGGL((step_kernel<K2, TS, K1, LK>), dim3(grid), dim3(256), 0, st, soa_of(s),
                      s->vfull_s.as<float4>(), LK ? nullptr : s->agrav_s.as<const float4>(),
-                     s->hasg_s.as<const int8_t>(), s->n, d2, dt, d1, rec, lk);
+                     s->hasg_s.as<const int8_t>(), s->n, d2, dt, d1, s->step.dev(), lk);
   SWH_HIP(hipGetLastError());
-  if (LK) SWH_TRY(couple_stage_end(s, LT_STEP, st));
-  SWH_HIP(hipMemcpyAsync(s->step_host.ptr, rec, REC_SLOTS * sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost, st));
-  SWH_HIP(hipEventRecord(s->step_event, st));
-  s->step_pending = true;
+  if (LK) SWH_TRY(s->link_timer.end(LT_STEP, st));
+  SWH_TRY(s->step.readback(st));
   if (TS) {
-    s->step_has_ts = true;
-    // host-only note next to the record: the dt_min of step_result's message
-    static_cast<double*>(s->step_host.ptr)[REC_SLOTS] = T->dt_min;
+    s->step.note_timestep(T->dt_min);
     // the pair lists hold the active particles of the bins they were built
     // with (list_mab only remembers max_active_bin): a bin may have changed.
     // keep_lists: the limited end of step walks them once more first -- the
@@ -466,14 +383,9 @@ swh_status space_kick1_linked(swh_space* s, const swh_kick_params* K1, const swh
 
 // The latest record's max |v_full| bounds the next drift's displacement.
 swh_status space_fetch_step_record(swh_space* s) {
-  if (!s->step_pending) return SWH_OK;
-  SWH_HIP(hipEventSynchronize(s->step_event));
-  const unsigned long long* h = static_cast<const unsigned long long*>(s->step_host.ptr);
-  const unsigned int vb = (unsigned int)h[REC_VMAX];
-  float vmax;
-  std::memcpy(&vmax, &vb, sizeof(vmax));
-  s->vfull_max = (double)vmax;
-  s->step_pending = false;
+  if (!s->step.pending) return SWH_OK;
+  SWH_TRY(s->step.fetch());
+  s->vfull_max = (double)s->step.vmax;
   return SWH_OK;
 }
 
@@ -530,26 +442,13 @@ swh_status swh_space_end_step_linked(swh_space* s, const swh_kick_params* K2,
 
 swh_status swh_space_step_result(swh_space* s, swh_step_result* out) {
   if (!s || !out) return SWH_ERR_ARG;
-  if (!s->step_has_ts) {
+  if (!s->step.has_ts) {
     set_error("swh_space_timestep or swh_space_end_step must precede swh_space_step_result");
     return SWH_ERR_STATE;
   }
   SWH_HIP(hipSetDevice(s->ctx->device));
   SWH_TRY(space_fetch_step_record(s));
-  const unsigned long long* h = static_cast<const unsigned long long*>(s->step_host.ptr);
-  out->ti_end_min = kMaxNrTimesteps - (int64_t)h[REC_END_MIN];
-  out->ti_end_max = (int64_t)h[REC_END_MAX];
-  out->ti_beg_max = (int64_t)h[REC_BEG_MAX];
-  out->n_updated = (int64_t)h[REC_UPDATED];
-  out->n_below_dt_min = (int64_t)h[REC_BELOW];
-  out->vfull_max = (float)s->vfull_max;
-  out->reserved = 0;
-  if (out->n_below_dt_min > 0) {
-    set_error("%lld parts want a time-step below dt_min (%e)", (long long)out->n_below_dt_min,
-              static_cast<const double*>(s->step_host.ptr)[REC_SLOTS]);
-    return SWH_ERR_ARG;
-  }
-  return SWH_OK;
+  return s->step.decode(out, "parts");
 }
 
 swh_status swh_space_download_xparts(swh_space* s, void* xparts, const swh_xpart_layout* XL,

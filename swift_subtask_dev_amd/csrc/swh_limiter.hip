@@ -22,7 +22,7 @@
 #include "swh_limiter.h"
 #include "swh_physics.h"
 #include "swh_space.h"
-#include "swh_wave.h"
+#include "swh_steprec.h"
 
 #pragma clang fp contract(off)
 
@@ -59,25 +59,29 @@ __global__ void wake_pack_kernel(const int* __restrict__ perm, const int* __rest
   out[perm ? perm[s] : s] = (int8_t)(wake ? wake[s] : kTimeBinNotAwake);
 }
 
-__device__ __forceinline__ long long wave_max_ll(long long v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const long long w = __shfl_xor(v, o);
-    v = w > v ? w : v;
+// The block's three counters, carried through the record's LDS exchange and
+// barrier (StepRecLane::commit): wave values in, one atomic each out; a block
+// that woke nothing leaves both records alone.
+struct LimCounts {
+  unsigned int n_act, n_inact, min_bin_c;  // this wave's
+  unsigned int (*sm)[4];                   // LDS, [3][4]
+  unsigned int* lim;
+  __device__ __forceinline__ void stage(int w) const {
+    sm[0][w] = n_act;
+    sm[1][w] = n_inact;
+    sm[2][w] = min_bin_c;
   }
-  return v;
-}
-__device__ __forceinline__ unsigned int wave_sum_u(unsigned int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ unsigned int wave_max_u(unsigned int v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned int)__shfl_xor(v, o));
-  return v;
-}
-// (an atomic only where it changes the word: the blocks' maxima mostly agree)
-__device__ __forceinline__ void atomic_max_u64_if(unsigned long long* p, unsigned long long v) {
-  if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
-}
+  __device__ __forceinline__ bool finish() const {
+    const unsigned int na = sm[0][0] + sm[0][1] + sm[0][2] + sm[0][3];
+    const unsigned int ni = sm[1][0] + sm[1][1] + sm[1][2] + sm[1][3];
+    if (na + ni == 0u) return false;  // nothing woken in this block
+    if (na) atomicAdd(lim + LIM_N_ACTIVE, na);
+    if (ni) atomicAdd(lim + LIM_N_INACTIVE, ni);
+    const unsigned int mb = max(max(sm[2][0], sm[2][1]), max(sm[2][2], sm[2][3]));
+    atomic_max_bits_if(lim + LIM_MIN_BIN_C, mb);
+    return true;
+  }
+};
 
 // runner_do_limiter over the owned, not inhibited particles whose wake-up word
 // is set: timestep_limit_part on the sorted SoA and xparts, the word reset,
@@ -93,12 +97,9 @@ __global__ __launch_bounds__(256) void limiter_apply_kernel(
     SoA a, float4* __restrict__ vfull, const float4* __restrict__ agrav,
     const int8_t* __restrict__ hasg, int* __restrict__ wake, int64_t n, LimiterKicks K,
     unsigned long long* __restrict__ rec, unsigned int* __restrict__ lim) {
-  __shared__ long long sm_t[3][4];
   __shared__ unsigned int sm_c[3][4];
-  __shared__ float sm_v[4];
-  long long end_min_c = 0, end_max = 0, beg_max = 0;
+  StepRecLane part;
   unsigned int n_act = 0, n_inact = 0, min_bin_c = 0;
-  float vmax = 0.f;
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
        s += (int64_t)gridDim.x * blockDim.x) {
     const int w = wake[s];
@@ -130,49 +131,16 @@ __global__ __launch_bounds__(256) void limiter_apply_kernel(
         ac.w = u_dt;
         a.acc[s] = ac;
       }
-      vmax = fmaxf(vmax, sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+      part.add_speed(sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
     }
-    const long long c = kMaxNrTimesteps - r.ti_end_new;
-    end_min_c = c > end_min_c ? c : end_min_c;
-    end_max = r.ti_end_new > end_max ? r.ti_end_new : end_max;
-    beg_max = r.ti_beg_new > beg_max ? r.ti_beg_new : beg_max;
+    part.add_times(r.ti_end_new, r.ti_beg_new);
     const unsigned int bc = (unsigned int)(127 - r.new_bin);
     min_bin_c = bc > min_bin_c ? bc : min_bin_c;
   }
-  const int wv = (int)(threadIdx.x >> 6);
-  const bool lead = (threadIdx.x & 63) == 0;
-  end_min_c = wave_max_ll(end_min_c);
-  end_max = wave_max_ll(end_max);
-  beg_max = wave_max_ll(beg_max);
-  n_act = wave_sum_u(n_act);
-  n_inact = wave_sum_u(n_inact);
-  min_bin_c = wave_max_u(min_bin_c);
-  for (int o = 32; o > 0; o >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, o));
-  if (lead) {
-    sm_t[0][wv] = end_min_c;
-    sm_t[1][wv] = end_max;
-    sm_t[2][wv] = beg_max;
-    sm_c[0][wv] = n_act;
-    sm_c[1][wv] = n_inact;
-    sm_c[2][wv] = min_bin_c;
-    sm_v[wv] = vmax;
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const unsigned int na = sm_c[0][0] + sm_c[0][1] + sm_c[0][2] + sm_c[0][3];
-  const unsigned int ni = sm_c[1][0] + sm_c[1][1] + sm_c[1][2] + sm_c[1][3];
-  if (na + ni == 0u) return;  // nothing woken in this block
-  for (int k = 0; k < 3; k++) {
-    long long m = sm_t[k][0];
-    for (int j = 1; j < 4; j++) m = sm_t[k][j] > m ? sm_t[k][j] : m;
-    if (m > 0) atomic_max_u64_if(rec + REC_END_MIN + k, (unsigned long long)m);
-  }
-  if (na) atomicAdd(lim + LIM_N_ACTIVE, na);
-  if (ni) atomicAdd(lim + LIM_N_INACTIVE, ni);
-  const unsigned int mb = max(max(sm_c[2][0], sm_c[2][1]), max(sm_c[2][2], sm_c[2][3]));
-  atomic_max_bits_if(lim + LIM_MIN_BIN_C, mb);
-  const float m = fmaxf(fmaxf(sm_v[0], sm_v[1]), fmaxf(sm_v[2], sm_v[3]));
-  if (m > 0.f) atomic_max_u64_if(rec + REC_VMAX, (unsigned long long)__float_as_uint(m));
+  const LimCounts counts{wave_sum_u(n_act), wave_sum_u(n_inact), wave_max_u(min_bin_c), sm_c,
+                         lim};
+  // (a merge: the record's two counters stay the time step's)
+  part.commit<kRecStrideSpace, true, true>(rec, 0u, 0u, counts);
 }
 
 swh_status fill_limiter(const swh_limiter_params* L, LimiterKicks* d) {
@@ -224,19 +192,8 @@ swh_status not_linked(const swh_space* s, const char* what) {
 }
 
 swh_status apply_ready(swh_space* s, const char* what) {
-  if (!s->xparts_valid) {
-    set_error("swh_space_upload_xparts must precede %s", what);
-    return SWH_ERR_STATE;
-  }
-  if (!s->has_ufull) {
-    set_error("%s needs u_full in the uploaded xparts (swh_xpart_layout.off_u_full)", what);
-    return SWH_ERR_ARG;
-  }
-  if (!s->built) {
-    set_error("swh_space_rebuild must precede %s", what);
-    return SWH_ERR_STATE;
-  }
-  if (!s->step_has_ts) {
+  SWH_TRY(step_ready(s, what));
+  if (!s->step.has_ts) {
     set_error("swh_space_timestep must precede %s: it merges into the time step's record", what);
     return SWH_ERR_STATE;
   }
@@ -250,21 +207,8 @@ swh_status limiter_loop(swh_space* s, const swh_hydro_params* P) {
   }
   SWH_HIP(hipSetDevice(s->ctx->device));
   SWH_TRY(ensure_wake(s));
+  s->wake_dirty = true;
   return space_limiter_walk(s, P);
-}
-
-// The entries for a linked space: a link, and (past the empty space) this
-// step's gravity pulled, as the linked kicks ask.
-swh_status need_link(const swh_space* s, const char* what) {
-  if (s->link) return SWH_OK;
-  set_error("swh_space_link_gspace must precede %s", what);
-  return SWH_ERR_STATE;
-}
-
-swh_status need_pull(const swh_space* s, const char* what) {
-  if (s->gp_pulled) return SWH_OK;
-  set_error("%s: no swh_space_pull_gravity since the last rebuild or upload", what);
-  return SWH_ERR_STATE;
 }
 
 // LK: the linked stage, the pulled a_grav of the gas gparts in the place of
@@ -280,6 +224,9 @@ swh_status limiter_apply(swh_space* s, const swh_limiter_params* L, const swh_hy
   LimiterKicks K;
   SWH_TRY(fill_limiter(L, &K));
   SWH_TRY(apply_ready(s, what));
+  // no loop since the last apply: every wake-up is still reset, and the step
+  // record and the counts of that apply stand as they are
+  if (s->lim_has && !s->wake_dirty) return SWH_OK;
   SWH_HIP(hipSetDevice(s->ctx->device));
   hipStream_t st = s->stream;
   SWH_TRY(space_ensure_xsorted(s));
@@ -288,23 +235,19 @@ swh_status limiter_apply(swh_space* s, const swh_limiter_params* L, const swh_hy
   SWH_TRY(s->lim_host.reserve(LIM_SLOTS * sizeof(unsigned int)));
   if (!s->lim_event) SWH_HIP(hipEventCreateWithFlags(&s->lim_event, hipEventDisableTiming));
   SWH_HIP(hipMemsetAsync(s->lim_rec.ptr, 0, LIM_SLOTS * sizeof(unsigned int), st));
-  unsigned long long* rec = s->step_rec.as<unsigned long long>();
   const int grid = (int)std::min<int64_t>((s->n + 255) / 256, 4 * kReduceBlocks);
   const float4* agrav = LK ? s->gp_agrav_s.as<const float4>() : s->agrav_s.as<const float4>();
   hipLaunchKernelGGL((limiter_apply_kernel<LK>), dim3(grid), dim3(256), 0, st, soa_of(s),
                      s->vfull_s.as<float4>(), agrav, s->hasg_s.as<const int8_t>(),
-                     s->wake_s.as<int>(), s->n, K, rec,
-                     s->lim_rec.as<unsigned int>());
+                     s->wake_s.as<int>(), s->n, K, s->step.dev(), s->lim_rec.as<unsigned int>());
   SWH_HIP(hipGetLastError());
   SWH_HIP(hipMemcpyAsync(s->lim_host.ptr, s->lim_rec.ptr, LIM_SLOTS * sizeof(unsigned int),
                          hipMemcpyDeviceToHost, st));
   SWH_HIP(hipEventRecord(s->lim_event, st));
   s->lim_has = true;
+  s->wake_dirty = false;
   // the merged step record, as every launch of the step kernel leaves it
-  SWH_HIP(hipMemcpyAsync(s->step_host.ptr, rec, REC_SLOTS * sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost, st));
-  SWH_HIP(hipEventRecord(s->step_event, st));
-  s->step_pending = true;
+  SWH_TRY(s->step.readback(st));
   // a woken particle may have entered the active bins without a list
   s->list_valid = false;
   s->list_check = false;

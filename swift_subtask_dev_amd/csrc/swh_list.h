@@ -849,7 +849,7 @@ __device__ __forceinline__ void list_walk(const GridDev& g, SoA& a, const ListDe
   }
   if (counter) {
     unsigned long long v = (unsigned long long)((act && s == 0) ? st.n : 0);
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum_ull(v);
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(counter_stripe(counter), v);
   }
 }

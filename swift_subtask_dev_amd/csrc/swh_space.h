@@ -73,10 +73,9 @@ swh_status space_xparts_to_caller(swh_space* s);
 // swh_kick.hip: wait for the latest step record, if one is queued, and take
 // its max |v_full| as the drift's displacement bound.
 swh_status space_fetch_step_record(swh_space* s);
-// Record slots of the step kernel (u64 each, all reduced by atomicMax /
-// atomicAdd from zero; REC_END_MIN holds max_nr_timesteps - ti_end_min). The
-// limiter's apply stage merges into the first three and REC_VMAX.
-enum { REC_END_MIN = 0, REC_END_MAX, REC_BEG_MAX, REC_UPDATED, REC_BELOW, REC_VMAX, REC_SLOTS = 8 };
+// swh_kick.hip: what a per-particle pass of the step (`what`) needs: the
+// xparts with u_full, and a rebuild.
+swh_status step_ready(swh_space* s, const char* what);
 // swh_kick.hip: kick2 + timestep in one launch that keeps the pair lists (the
 // limiter walks them before they are dropped), and kick1.
 swh_status space_kick2_timestep_keep_lists(swh_space* s, const swh_kick_params* K2,

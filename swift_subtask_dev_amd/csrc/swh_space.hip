@@ -17,6 +17,7 @@
 #include "swh_internal.h"
 #include "swh_physics.h"
 #include "swh_space.h"
+#include "swh_steprec.h"
 #include "swh_wave.h"
 
 namespace swh {
@@ -746,13 +747,11 @@ swh_status swh_space_destroy(swh_space* s) {
                     &s->ghost_right, &s->ghost_list, &s->ghost_list2, &s->ghost_search, &s->ghost_seg, &s->grown_q,
                     &s->grown_mark, &s->grown_search,
                     &s->nbr, &s->nbr_cnt, &s->nbr_base, &s->nbr_reach, &s->nbr_ovf, &s->posf, &s->gplan, &s->ctr_stripes,
-                    &s->iperm, &s->vfull_s, &s->agrav_s, &s->hasg_s, &s->list_xd0,
-                    &s->step_rec};
+                    &s->iperm, &s->vfull_s, &s->agrav_s, &s->hasg_s, &s->list_xd0};
   for (DevBuf* b : bufs) b->release();
   couple_release(s);
   limiter_release(s);
-  s->step_host.release();
-  if (s->step_event) (void)hipEventDestroy(s->step_event);
+  s->step.release();
   s->hstage.release();
   s->ghost_host.release();
   if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
@@ -859,8 +858,7 @@ swh_status swh_space_upload_xparts(swh_space* s, const void* xparts, int64_t cou
   s->xparts_valid = true;
   s->xsorted_valid = false;
   s->has_ufull = XL->off_u_full >= 0;
-  s->step_pending = false;  // records of kicks before this upload are void
-  s->step_has_ts = false;
+  s->step.invalidate();  // records of kicks before this upload are void
   return SWH_OK;
 }
 
@@ -945,10 +943,10 @@ swh_status swh_space_upload_parts(swh_space* s, const void* parts, int64_t count
   SWH_TRY(s->hasg_c.reserve((size_t)count));
   s->xparts_valid = false;
   s->xsorted_valid = false;
-  s->step_pending = false;
-  s->step_has_ts = false;
+  s->step.invalidate();
   s->wake_sorted = s->wake_caller = false;  // every particle starts not awake
   s->lim_has = false;
+  s->wake_dirty = false;
   s->grid.dx = 0.;
   hipLaunchKernelGGL(unpack_kernel, dim3(grid), dim3(block), 0, s->stream, L,
                      s->aos.as<const char>(), count, soa_of(s), s->hasg_c.as<int8_t>());

@@ -37,6 +37,11 @@ SWH_HD int get_time_bin(int64_t step) {
   return 62 - (int)__builtin_clzll((unsigned long long)step);
 }
 
+// The row of a per-bin table (the kicks' half-steps, one entry per bin from 0
+// to num_time_bins) for time bin `bin`.
+constexpr int kBinTable = kTimelineBins + 1;
+SWH_HD int kick_bin(int bin) { return bin < 0 ? 0 : (bin >= kBinTable ? kBinTable - 1 : bin); }
+
 // Start of the step of bin `bin` that holds ti_current (ti_current itself
 // counts as the end of the step before it).
 SWH_HD int64_t get_integer_time_begin(int64_t ti_current, int bin) {

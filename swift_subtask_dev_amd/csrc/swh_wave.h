@@ -18,13 +18,40 @@ namespace swh {
 __device__ __forceinline__ void atomic_max_bits_if(unsigned int* p, unsigned int v) {
   if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
 }
+__device__ __forceinline__ void atomic_max_u64_if(unsigned long long* p, unsigned long long v) {
+  if (v > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, v);
+}
 __device__ __forceinline__ void atomic_flag_if(unsigned int* p) {
   if (__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) atomicOr(p, 1u);
+}
+// Sums and maxima over the 64 lanes of a wave (every lane must call them).
+__device__ __forceinline__ unsigned int wave_sum_u(unsigned int v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_ull(unsigned long long v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ unsigned int wave_max_u(unsigned int v) {
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned int)__shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ long long wave_max_ll(long long v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const long long w = __shfl_xor(v, o);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ float wave_max_f(float v) {
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
 }
 // Max of v over a 256-thread block (every thread must call it), then one
 // conditional atomic per block on p (float bits, v >= 0). sm: 4 floats of LDS.
 __device__ __forceinline__ void block_max_bits(unsigned int* p, float v, float* sm) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  v = wave_max_f(v);
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {

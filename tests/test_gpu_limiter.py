@@ -224,6 +224,95 @@ def test_apply_cosmological_tables(gpu_ctx):
     assert d > 1e3 * np.abs(gx["v_full"][inact] - ox["v_full"][inact]).max()
 
 
+def _pick_sparse(parts):
+    """A shocked starting particle i, a sleeper j of bin >= 8 + 40 well inside
+    H_i, and four more sleepers far from i: all that stays live."""
+    tb = parts["time_bin"].astype(np.int64)
+    hig2 = RL.hig2_of(parts)
+    for i in range(0, len(parts), 11):
+        if tb[i] > MAB:
+            continue
+        r2 = RL.pair_r2(parts, i, (1.0, 1.0, 1.0), True)
+        sleepers = (tb >= 8 + SHIFT) & (tb != abi.TIME_BIN_INHIBITED)
+        near = np.flatnonzero(sleepers & (r2 < 0.25 * hig2[i]))
+        far = np.flatnonzero(sleepers & (r2 > 0.3 ** 2))
+        if near.size and far.size >= 4:
+            return i, int(near[0]), far[:4]
+    raise AssertionError("no such pair in the state")
+
+
+def _sparse_apply(gpu_ctx):
+    """Time step, loop and apply on six live particles of which the loop wakes
+    one sleeper; then a second apply, with nothing woken. Every expectation is
+    the reference's."""
+    parts, xp, P, T = _state(gpu_ctx)
+    i, j, far = _pick_sparse(parts)
+    keep = np.concatenate([[i, j], far])
+    dead = np.ones(len(parts), bool)
+    dead[keep] = False
+    parts["time_bin"][dead] = abi.TIME_BIN_INHIBITED
+    xp["v_full"][j] = (-2.0, 0.0, 0.0)  # the fastest; its re-kick speeds it up
+    live = ~dead
+    sp = KC.open_space(gpu_ctx, parts, xp, P)
+    b0, _ = KC.fetch(sp, parts, xp)
+    sp.timestep(T, P)
+    rec0 = sp.step_result()
+    sp.limiter_loop(P)
+    w = sp.download_wakeup()
+    b, bx = KC.fetch(sp, parts, xp)
+    L = _limiter_params()
+    sp.limiter_apply(L, P)
+    rec, lr = sp.step_result(), sp.limiter_result()
+    g, gx = KC.fetch(sp, parts, xp)
+    sp.limiter_apply(L, P)  # every wake-up was reset: nothing to do
+    rec2, lr2 = sp.step_result(), sp.limiter_result()
+    g2, gx2 = KC.fetch(sp, parts, xp)
+    sp.close()
+    # the time step's own record, of six particles
+    act0 = live & (b0["time_bin"] <= MAB)
+    assert act0.sum() == 1 and act0[i]
+    want0 = R.step_record(b0["time_bin"], b["time_bin"], act0, live, TI)
+    assert {k: rec0[k] for k in want0} == want0
+    v0 = float(np.sqrt((bx["v_full"][live].astype(np.float64) ** 2).sum(axis=1)).max())
+    assert abs(rec0["vfull_max"] - v0) <= 1e-6 * v0
+    # the loop woke the sleeper and nobody else
+    assert np.array_equal(w, RL.wakeup_loop(b, MAB))
+    assert np.array_equal(np.flatnonzero(w != N_A), [j])
+    o, ox = abi.copy_parts(b), bx.copy()
+    woken, wact, ti_end, ti_beg, _ = RL.limit_part(o, ox, w, TI, TIME_BASE, MAB)
+    assert woken.sum() == 1 and woken[j] and not wact.any()
+    KC.check_kick(g, gx, o, ox, b, bx, woken, reset=False, what="sparse apply")
+    assert np.array_equal(g["time_bin"], o["time_bin"])
+    want = RL.merge_record({k: rec0[k] for k in ("ti_end_min", "ti_end_max", "ti_beg_max")},
+                           woken, ti_end, ti_beg)
+    vj = float(np.sqrt((ox["v_full"][j].astype(np.float64) ** 2).sum()))
+    assert vj > 2.0  # the merge has a max |v_full| to raise
+    print("sparse apply: record", rec0, "->", rec, "wanted", want, "|v_j|", vj)
+    print("limiter_result", lr, "after the second apply", lr2)
+    assert {k: rec[k] for k in want} == want
+    assert rec["n_updated"] == rec0["n_updated"] == 1 and rec["n_below_dt_min"] == 0
+    assert abs(rec["vfull_max"] - max(v0, vj)) <= 1e-6 * max(v0, vj)
+    assert lr == {"n_woken_active": 0, "n_woken_inactive": 1, "min_new_bin": int(o["time_bin"][j])}
+    # the second apply changed no particle
+    assert KC.same_records(g2, g) and KC.same_records(gx2, gx)
+    return rec, lr, rec2, lr2
+
+
+def test_apply_merges_into_sparse_record(gpu_ctx):
+    """The apply stage's merge where one lane of one block has something to
+    add; a second apply, with nothing woken, leaves the step record as it is."""
+    rec, lr, rec2, lr2 = _sparse_apply(gpu_ctx)
+    assert rec2 == rec
+
+
+def test_second_apply_keeps_limiter_result(gpu_ctx):
+    """A second apply with no loop since the first (nothing can be woken)
+    leaves swh_space_limiter_result unchanged: the counts stay those of the
+    apply that had wake-ups to work on."""
+    rec, lr, rec2, lr2 = _sparse_apply(gpu_ctx)
+    assert lr2 == lr
+
+
 def _end_of_step(gpu_ctx, fused, tuning):
     parts, xp, P, T = _state(gpu_ctx, hot=True)
     K = KC.kick_params(TI, TIME_BASE, MAB)

@@ -6,7 +6,16 @@ time_bin is an integer decision: it must equal the reference's exactly,
 except where the reference's new_dt * time_base_inv lies within 4 float ulps
 (relative 4.8e-7) of a power of two, where the bin of either side passes; at
 most 4 of the 4,096 particles may use that exception. The record is compared
-exactly with the reference record computed from the GPU's own bins."""
+exactly with the reference record computed from the GPU's own bins.
+
+The sparse cases run the record's reduction where most lanes, waves and blocks
+have nothing to add: all but k particles inhibited (a rebuild sorts inhibited
+particles behind the live ones, so these fill the first k lanes of the grid:
+one lane, a wave less one lane, a wave and one lane, a block and one lane, and
+every block after them adds nothing), or all but k particles foreign (they
+stay where the sort put them: the k owned ones, a regular sample of the caller
+order, lie scattered over the sixteen blocks among lanes that add their speed
+only)."""
 from __future__ import annotations
 
 import numpy as np
@@ -31,10 +40,16 @@ def _params(**kw):
     return T
 
 
-def _state(ctx):
+def _state(ctx, keep=None):
+    """keep: the caller indices that stay live (default: all but every 13th)."""
     parts, P = KC.stepped_state(ctx, OLD_BINS)
     xp = KC.make_xparts(parts)
-    parts["time_bin"][::13] = abi.TIME_BIN_INHIBITED
+    if keep is None:
+        parts["time_bin"][::13] = abi.TIME_BIN_INHIBITED
+    else:
+        dead = np.ones(len(parts), bool)
+        dead[np.asarray(keep)] = False
+        parts["time_bin"][dead] = abi.TIME_BIN_INHIBITED
     P.max_active_bin = R.get_max_active_bin(TI)
     assert P.max_active_bin == 50
     return parts, xp, P
@@ -171,3 +186,112 @@ def test_end_step_equals_separate_launches(gpu_ctx):
     vmax = np.sqrt((x1["v_full"][b["time_bin"] != abi.TIME_BIN_INHIBITED].astype(np.float64) ** 2)
                    .sum(axis=1)).max()
     assert abs(r1["vfull_max"] - vmax) <= 1e-6 * vmax
+
+
+def _spread(k, pool):
+    """k of the indices `pool`, evenly spaced."""
+    return pool[np.round(np.linspace(0, len(pool) - 1, k)).astype(np.int64)]
+
+
+def _sparse_case(ctx, case):
+    """(parts, xp, P, live, owned, n_owned): live: not inhibited; owned: the
+    particles of the record (live and not foreign)."""
+    n = 16 ** 3
+    layout, k = case.split("_")
+    if layout in ("first", "last"):
+        keep = np.array([0 if layout == "first" else n - 1])
+    else:
+        keep = _spread(int(k), np.arange(n))
+    if layout == "foreign":
+        # the k first: swh_space_set_owned takes a prefix of the caller order
+        parts, xp, P = _state(ctx, keep=np.arange(n))
+        order = np.concatenate([keep, np.setdiff1d(np.arange(n), keep)])
+        parts, xp = parts[order].copy(), xp[order].copy()
+        live = np.ones(n, bool)
+        owned = np.arange(n) < len(keep)
+        return parts, xp, P, live, owned, len(keep)
+    if layout == "inactive":  # every survivor sleeps through this step
+        parts, _, _ = _state(ctx, keep=np.arange(n))
+        keep = _spread(int(k), np.flatnonzero(parts["time_bin"] == 52))
+    parts, xp, P = _state(ctx, keep=keep)
+    live = parts["time_bin"] != abi.TIME_BIN_INHIBITED
+    assert live.sum() == len(keep)
+    return parts, xp, P, live, live, n
+
+
+def _vmax(xp, live):
+    return float(np.sqrt((xp["v_full"][live].astype(np.float64) ** 2).sum(axis=1)).max())
+
+
+SPARSE = ["first_1", "last_1", "inhibited_63", "inhibited_65", "inhibited_257", "foreign_65",
+          "foreign_257", "inactive_65"]
+
+
+@pytest.mark.parametrize("case", SPARSE)
+def test_record_with_few_live_particles(gpu_ctx, case):
+    """swh_space_timestep, and separately the fused swh_space_end_step, where
+    few particles have anything to add to the record (see the module's text):
+    the record equals the reference record of the GPU's own bins exactly,
+    vfull_max the float max |v_full| of the live particles to 1e-6."""
+    parts, xp, P, live, owned, n_owned = _sparse_case(gpu_ctx, case)
+    T = _params()
+    K = KC.kick_params(TI, 1.0 / TBI, P.max_active_bin)
+    for fused in (False, True):
+        sp = KC.open_space(gpu_ctx, parts, xp, P)
+        sp.set_owned(n_owned)
+        b, bx = KC.fetch(sp, parts, xp)
+        if fused:
+            sp.end_step(K, T, K, P)
+        else:
+            sp.timestep(T, P)
+        res = sp.step_result()
+        g, gx = KC.fetch(sp, parts, xp)
+        sp.close()
+        act = owned & (b["time_bin"] <= P.max_active_bin)
+        print(case, "fused" if fused else "timestep", res, "active", int(act.sum()))
+        _check_record(res, b, g, act, owned, np.zeros(len(b), bool))
+        assert np.array_equal(g["time_bin"][~act], b["time_bin"][~act])
+        vmax = _vmax(gx, live)
+        assert abs(res["vfull_max"] - vmax) <= 1e-6 * vmax
+        if fused:
+            assert (gx["v_full"][act] != bx["v_full"][act]).any() or not act.any()
+        else:
+            assert np.array_equal(gx["v_full"], bx["v_full"])
+        if case.startswith("inactive"):
+            assert res["n_updated"] == 0 and not act.any()
+            assert res["ti_end_min"] == res["ti_end_max"] == int(R.get_integer_time_end(TI, 52))
+            assert res["ti_beg_max"] == int(R.get_integer_time_begin(TI + 1, 52))
+        else:
+            assert res["n_updated"] == int(act.sum()) > 0
+
+
+def test_kicks_keep_the_timestep_fields(gpu_ctx):
+    """A kick after a time step measures max |v_full| anew and leaves the
+    record's five time fields as the time step wrote them."""
+    parts, xp, P = _state(gpu_ctx)
+    live = parts["time_bin"] != abi.TIME_BIN_INHIBITED
+    # the fastest particle is one that both kicks move: it stays active (a new
+    # bin is at most the old one + 1) and gains at least 50 * 2^-13 per kick
+    j = int(np.flatnonzero(live & (parts["time_bin"] <= 49))[0])
+    xp["v_full"][j] = (3.0, 0.0, 0.0)
+    xp["a_grav"][j] = (50.0, 0.0, 0.0)
+    parts["a_hydro"][j] = 0.0
+    parts["gpart"][j] = 1
+    K = KC.kick_params(TI, 1.0 / TBI, P.max_active_bin)
+    sp = KC.open_space(gpu_ctx, parts, xp, P)
+    sp.timestep(_params(), P)
+    res0 = sp.step_result()
+    v0 = _vmax(xp, live)
+    assert abs(res0["vfull_max"] - v0) <= 1e-6 * v0
+    seen = [res0["vfull_max"]]
+    for kick in (sp.kick1, sp.kick2):
+        kick(K, P)
+        res = sp.step_result()
+        _, gx = KC.fetch(sp, parts, xp)
+        for f in ("ti_end_min", "ti_end_max", "ti_beg_max", "n_updated", "n_below_dt_min"):
+            assert res[f] == res0[f], f
+        vmax = _vmax(gx, live)
+        assert abs(res["vfull_max"] - vmax) <= 1e-6 * vmax
+        assert res["vfull_max"] not in seen  # the kick's own, not an earlier launch's
+        seen.append(res["vfull_max"])
+    sp.close()
