@@ -294,7 +294,11 @@ SWH_API swh_status swh_space_rebuild(swh_space *s, const swh_hydro_params *P,
                              double min_cell_width);
 
 /* Loops over all active particles. n_interactions (optional) receives the
- * number of directed interactions evaluated (r < H_i, resp. max(H_i,H_j)). */
+ * number of directed interactions evaluated (r < H_i, resp. max(H_i,H_j)).
+ * swh_space_init_parts (hydro_init_part on active parts) and
+ * swh_space_reset_acceleration launch nothing themselves: the density (force)
+ * loop that follows folds the operation into its stores, and any other call on
+ * the space applies it first, so every call sees the fields as if it had run. */
 SWH_API swh_status swh_space_init_parts(swh_space *s, const swh_hydro_params *P);
 /* hydro_reset_acceleration + timestep_limiter_prepare_force on active parts
  * (what the extra ghost does before the force loop). */

@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void pull_kernel(CoupleLayout L, const char* _
 __global__ __launch_bounds__(256) void push_kernel(CoupleLayout L, char* __restrict__ aos,
                                                    int64_t ng, int64_t n,
                                                    const int* __restrict__ iperm,
-                                                   const double4* __restrict__ pos,
+                                                   const PosRec* __restrict__ pos,
                                                    const float4* __restrict__ vfull,
                                                    const int8_t* __restrict__ tb, uint32_t what,
                                                    int periodic, double dim0, double dim1,
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256) void push_kernel(CoupleLayout L, char* __restr
     double x[3] = {0., 0., 0.};
     float v[3] = {0.f, 0.f, 0.f};
     if (what & kPushX) {
-      const double4 p = pos[s];
+      const PosRec p = pos[s];
       x[0] = p.x, x[1] = p.y, x[2] = p.z;
     }
     if (what & kPushVFull) {
@@ -215,6 +215,7 @@ using namespace swh;
 extern "C" {
 
 swh_status swh_space_link_gspace(swh_space* s, swh_gspace* g, int64_t* n_linked) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s) return SWH_ERR_ARG;
   if (n_linked) *n_linked = 0;
   if (!g) {
@@ -295,6 +296,7 @@ swh_status swh_space_link_gspace(swh_space* s, swh_gspace* g, int64_t* n_linked)
 }
 
 swh_status swh_space_pull_gravity(swh_space* s) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s) return SWH_ERR_ARG;
   SWH_TRY(linked(s, "swh_space_pull_gravity"));
   swh_gspace* g = s->link;
@@ -318,6 +320,7 @@ swh_status swh_space_pull_gravity(swh_space* s) {
 }
 
 swh_status swh_space_push_gparts(swh_space* s, const swh_push_params* Q) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || !Q) return SWH_ERR_ARG;
   if (Q->what & ~(SWH_PUSH_X | SWH_PUSH_V_FULL | SWH_PUSH_TIME_BIN)) {
     set_error("swh_space_push_gparts: unknown bits in what (%u)", Q->what);
@@ -339,7 +342,7 @@ swh_status swh_space_push_gparts(swh_space* s, const swh_push_params* Q) {
   SWH_TRY(s->link_timer.begin(LT_PUSH, g->stream));
   hipLaunchKernelGGL(push_kernel, dim3(couple_grid(g->n)), dim3(256), 0, g->stream, L,
                      g->aos.as<char>(), g->n, s->n, s->iperm.as<const int>(),
-                     s->pos.as<const double4>(), s->vfull_s.as<const float4>(),
+                     s->pos.as<const PosRec>(), s->vfull_s.as<const float4>(),
                      s->tb.as<const int8_t>(), Q->what, Q->periodic, Q->dim[0], Q->dim[1],
                      Q->dim[2]);
   SWH_HIP(hipGetLastError());

@@ -8,7 +8,9 @@
 //   store()    : accumulate into the particle's fields (SWIFT "+=" semantics)
 //   kPay / load_j() / interact_staged(): the j-side record a list walk loads
 //                (kPay float4s + one int) and the iact on it; load_j<true>
-//                gathers with 32-bit byte offsets (gather_at)
+//                gathers with 32-bit byte offsets (gather_at). It is given
+//                j's position record: the force state takes j's time bin
+//                from it (bin_of), not from a gather of tb[j]
 // A fourth state, the time-step limiter's, gathers the same way and scatters
 // wake-ups instead of accumulating (r < H_i).
 //
@@ -67,16 +69,18 @@ struct LoopState<LOOP_DENSITY, T> {
   double reach;
   T hig2, hi_inv, vix, viy, viz;
   DensityAcc<T> A;
-  __device__ __forceinline__ void load_i(const SoA& a, int i, T, const unsigned int*) {
-    const double4 p = a.pos[i];
+  template <typename Ix>
+  __device__ __forceinline__ void load_i(const SoA& a, Ix i, T, const unsigned int*,
+                                         bool = false) {
+    const PosRec p = a.pos[i];
     const float4 vm = a.vm[i];
-    const T hi = (T)p.w;
-    self = i;
+    const T hi = (T)h_of(p);
+    self = (int)i;
     n = 0;
     hig2 = hi * hi * (T)kGamma2;
     hi_inv = (T)1 / hi;
     vix = vm.x; viy = vm.y; viz = vm.z;
-    reach = p.w * (double)kGamma;
+    reach = (double)h_of(p) * (double)kGamma;
     A.zero();
   }
   __device__ __forceinline__ void iact(T r2, T dx, T dy, T dz, T mj, T vjx, T vjy, T vjz) {
@@ -85,10 +89,10 @@ struct LoopState<LOOP_DENSITY, T> {
     else
       iact_nonsym_density<T>(r2, dx, dy, dz, hi_inv, vix, viy, viz, mj, vjx, vjy, vjz, A);
   }
-  __device__ __forceinline__ bool accept(int j, const double4&, T r2) const {
+  __device__ __forceinline__ bool accept(int j, const PosRec&, T r2) const {
     return (r2 < hig2) & (j != self);
   }
-  __device__ __forceinline__ void interact(const SoA& a, int j, const double4&, T dx, T dy,
+  __device__ __forceinline__ void interact(const SoA& a, int j, const PosRec&, T dx, T dy,
                                            T dz, T r2) {
     const float4 v = a.vm[j];
     iact(r2, dx, dy, dz, (T)v.w, (T)v.x, (T)v.y, (T)v.z);
@@ -96,23 +100,32 @@ struct LoopState<LOOP_DENSITY, T> {
   }
   static constexpr int kPay = 1;
   template <bool O32 = false>  // (the density walk gathers by plain indexing)
-  __device__ static __forceinline__ JRec<1> load_j(const SoA& a, int j) {
+  __device__ static __forceinline__ JRec<1> load_j(const SoA& a, int j, const PosRec& pj) {
     JRec<1> r;
     r.p[0] = a.vm[j];
     r.meta = 0;
     return r;
   }
-  __device__ __forceinline__ void interact_staged(const float4* p, int, const double4&, T dx,
+  __device__ __forceinline__ void interact_staged(const float4* p, int, const PosRec&, T dx,
                                                   T dy, T dz, T r2) {
     iact(r2, dx, dy, dz, (T)p[0].w, (T)p[0].x, (T)p[0].y, (T)p[0].z);
     n++;
   }
-  __device__ __forceinline__ void store(SoA& a, int i) const {
+  // fused: a pending hydro_init_part is folded into the store (store_init's
+  // values stand in for the loads; the sums are added to them as ever)
+  template <typename Ix>
+  __device__ __forceinline__ void store(SoA& a, Ix i, bool fused = false) const {
     DensityAcc<T> A = this->A;
     if constexpr (kRaw) A = density_finalize(this->A);
-    float4 d = a.dens[i];
-    float4 r = a.rot[i];
-    a.th[i].y = (float)((T)a.th[i].y + A.rho);
+    float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
+    float rho = 0.f;
+    if (!fused) {
+      d = a.dens[i];
+      r = a.rot[i];
+      rho = a.th[i].y;
+    }
+    a.th[i].y = (float)((T)rho + A.rho);
     d.x = (float)((T)d.x + A.rho_dh);
     d.y = (float)((T)d.y + A.wcount);
     d.z = (float)((T)d.z + A.wcount_dh);
@@ -123,6 +136,13 @@ struct LoopState<LOOP_DENSITY, T> {
     a.dens[i] = d;
     a.rot[i] = r;
   }
+  // hydro_init_part (init_kernel) for one particle
+  template <typename Ix>
+  __device__ static __forceinline__ void store_init(SoA& a, Ix i) {
+    a.th[i].y = 0.f;
+    a.dens[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    a.rot[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
 };
 
 template <typename T>
@@ -132,30 +152,32 @@ struct LoopState<LOOP_GRADIENT, T> {
   T hi, hig2, vix, viy, viz, ui, ci, a2H;
   float gz, gw;
   GradientAcc<T> A;
-  __device__ __forceinline__ void load_i(const SoA& a, int i, T a2H_, const unsigned int*) {
-    const double4 p = a.pos[i];
+  template <typename Ix>
+  __device__ __forceinline__ void load_i(const SoA& a, Ix i, T a2H_, const unsigned int*,
+                                         bool = false) {
+    const PosRec p = a.pos[i];
     const float4 vm = a.vm[i];
     const float4 th = a.th[i];
     const float4 g = a.grad[i];
-    self = i;
+    self = (int)i;
     n = 0;
-    hi = (T)p.w;
+    hi = (T)h_of(p);
     hig2 = hi * hi * (T)kGamma2;
     vix = vm.x; viy = vm.y; viz = vm.z;
     ui = th.x;
     ci = th.w;
     a2H = a2H_;
-    reach = p.w * (double)kGamma;
+    reach = (double)h_of(p) * (double)kGamma;
     A.v_sig = g.x;
     A.alpha_visc_max_ngb = g.y;
     A.laplace_u = (T)0;
     gz = g.z;
     gw = g.w;
   }
-  __device__ __forceinline__ bool accept(int j, const double4&, T r2) const {
+  __device__ __forceinline__ bool accept(int j, const PosRec&, T r2) const {
     return (r2 < hig2) & (j != self);
   }
-  __device__ __forceinline__ void interact(const SoA& a, int j, const double4&, T dx, T dy,
+  __device__ __forceinline__ void interact(const SoA& a, int j, const PosRec&, T dx, T dy,
                                            T dz, T r2) {
     const float4 v = a.vm[j];
     const float4 t = a.th[j];
@@ -165,7 +187,7 @@ struct LoopState<LOOP_GRADIENT, T> {
   }
   static constexpr int kPay = 2;
   template <bool O32 = false>  // (the gradient walk gathers by plain indexing)
-  __device__ static __forceinline__ JRec<2> load_j(const SoA& a, int j) {
+  __device__ static __forceinline__ JRec<2> load_j(const SoA& a, int j, const PosRec& pj) {
     const float4 t = a.th[j];
     JRec<2> r;
     r.p[0] = a.vm[j];
@@ -173,17 +195,19 @@ struct LoopState<LOOP_GRADIENT, T> {
     r.meta = 0;
     return r;
   }
-  __device__ __forceinline__ void interact_staged(const float4* p, int, const double4&, T dx,
+  __device__ __forceinline__ void interact_staged(const float4* p, int, const PosRec&, T dx,
                                                   T dy, T dz, T r2) {
     iact_nonsym_gradient<T>(r2, dx, dy, dz, hi, vix, viy, viz, ui, ci, (T)p[0].w, (T)p[0].x,
                             (T)p[0].y, (T)p[0].z, (T)p[1].x, (T)p[1].y, (T)p[1].z, (T)p[1].w,
                             a2H, A);
     n++;
   }
-  __device__ __forceinline__ void store(SoA& a, int i) const {
+  template <typename Ix>
+  __device__ __forceinline__ void store(SoA& a, Ix i, bool = false) const {
     a.grad[i] = make_float4((float)A.v_sig, (float)A.alpha_visc_max_ngb, gz, gw);
     a.rot[i].w = (float)((T)a.rot[i].w + A.laplace_u);
   }
+  __device__ static __forceinline__ void store_init(SoA&, int) {}  // (never fused)
 };
 
 template <typename T>
@@ -193,14 +217,17 @@ struct LoopState<LOOP_FORCE, T> {
   T hig2, hi_inv, hid_inv, a2H;
   ForceIn<T> I;
   ForceAcc<T> A;
-  __device__ __forceinline__ void load_i(const SoA& a, int i, T a2H_,
-                                         const unsigned int* hmax_bits) {
-    const double4 p = a.pos[i];
+  // fused: a pending hydro_reset_acceleration is folded into the loop
+  // (min_ngb_time_bin starts from its reset value, not from memory)
+  template <typename Ix>
+  __device__ __forceinline__ void load_i(const SoA& a, Ix i, T a2H_,
+                                         const unsigned int* hmax_bits, bool fused = false) {
+    const PosRec p = a.pos[i];
     const float4 vm = a.vm[i];
     const float4 th = a.th[i];
     const float4 fc = a.fc[i];
-    const T hi = (T)p.w;
-    self = i;
+    const T hi = (T)h_of(p);
+    self = (int)i;
     n = 0;
     hig2 = hi * hi * (T)kGamma2;
     hi_inv = (T)1 / hi;
@@ -213,59 +240,71 @@ struct LoopState<LOOP_FORCE, T> {
     I.f = fc.x; I.balsara = fc.y; I.alpha_visc = fc.z; I.alpha_diff = fc.w;
     force_prep_i(I);
     A.ax = A.ay = A.az = A.u_dt = A.h_dt = (T)0;
-    A.min_ngb_time_bin = a.mintb[i];
+    A.min_ngb_time_bin = kNumTimeBins + 1;
+    if (!fused) A.min_ngb_time_bin = a.mintb[i];
     const double hmax = (double)__uint_as_float(*hmax_bits) * (double)kGamma;
-    reach = fmax(hmax, p.w * (double)kGamma);
+    reach = fmax(hmax, (double)h_of(p) * (double)kGamma);
   }
-  __device__ __forceinline__ bool accept(int j, const double4& pj, T r2) const {
-    const T hj = (T)pj.w;
+  __device__ __forceinline__ bool accept(int j, const PosRec& pj, T r2) const {
+    const T hj = (T)h_of(pj);
     return ((r2 < hig2) | (r2 < hj * hj * (T)kGamma2)) & (j != self);
   }
-  __device__ __forceinline__ void interact(const SoA& a, int j, const double4& pj, T dx, T dy,
+  __device__ __forceinline__ void interact(const SoA& a, int j, const PosRec& pj, T dx, T dy,
                                            T dz, T r2) {
     ForceIn<T> J;
     const float4 v = a.vm[j];
     const float4 t = a.th[j];
     const float4 c = a.fc[j];
     J.vx = v.x; J.vy = v.y; J.vz = v.z; J.m = v.w;
-    J.h = (T)pj.w;
+    J.h = (T)h_of(pj);
     J.u = t.x; J.rho = t.y; J.P = t.z; J.c = t.w;
     J.f = c.x; J.balsara = c.y; J.alpha_visc = c.z; J.alpha_diff = c.w;
     iact_nonsym_force<T>(r2, dx, dy, dz, I, hid_inv, hi_inv, J, a2H, A);
-    const int tbj = a.tb[j];
+    const int tbj = bin_of(pj);
     if (tbj > 0 && tbj < A.min_ngb_time_bin) A.min_ngb_time_bin = tbj;
     n++;
   }
   static constexpr int kPay = 3;
   template <bool O32 = false>
-  __device__ static __forceinline__ JRec<3> load_j(const SoA& a, int j) {
+  __device__ static __forceinline__ JRec<3> load_j(const SoA& a, int j, const PosRec& pj) {
     JRec<3> r;
     r.p[0] = gather_at<O32>(a.vm, j);
     r.p[1] = gather_at<O32>(a.th, j);
     r.p[2] = gather_at<O32>(a.fc, j);
-    r.meta = gather_at<O32>(a.tb, j);
+    r.meta = bin_of(pj);  // (the bin travels with the position: no gather of its own)
     return r;
   }
-  __device__ __forceinline__ void interact_staged(const float4* p, int tbj, const double4& pj,
+  __device__ __forceinline__ void interact_staged(const float4* p, int tbj, const PosRec& pj,
                                                   T dx, T dy, T dz, T r2) {
     ForceIn<T> J;
     J.vx = p[0].x; J.vy = p[0].y; J.vz = p[0].z; J.m = p[0].w;
-    J.h = (T)pj.w;
+    J.h = (T)h_of(pj);
     J.u = p[1].x; J.rho = p[1].y; J.P = p[1].z; J.c = p[1].w;
     J.f = p[2].x; J.balsara = p[2].y; J.alpha_visc = p[2].z; J.alpha_diff = p[2].w;
     iact_nonsym_force<T>(r2, dx, dy, dz, I, hid_inv, hi_inv, J, a2H, A);
     if (tbj > 0 && tbj < A.min_ngb_time_bin) A.min_ngb_time_bin = tbj;
     n++;
   }
-  __device__ __forceinline__ void store(SoA& a, int i) const {
-    float4 ac = a.acc[i];
+  template <typename Ix>
+  __device__ __forceinline__ void store(SoA& a, Ix i, bool fused = false) const {
+    float4 ac = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!fused) ac = a.acc[i];
     ac.x = (float)((T)ac.x + A.ax);
     ac.y = (float)((T)ac.y + A.ay);
     ac.z = (float)((T)ac.z + A.az);
     ac.w = (float)((T)ac.w + A.u_dt);
     a.acc[i] = ac;
-    a.hdt[i] = (float)((T)a.hdt[i] + A.h_dt);
+    float hdt = 0.f;
+    if (!fused) hdt = a.hdt[i];
+    a.hdt[i] = (float)((T)hdt + A.h_dt);
     a.mintb[i] = (int8_t)A.min_ngb_time_bin;
+  }
+  // hydro_reset_acceleration (reset_acc_kernel) for one particle
+  template <typename Ix>
+  __device__ static __forceinline__ void store_init(SoA& a, Ix i) {
+    a.acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    a.hdt[i] = 0.f;
+    a.mintb[i] = (int8_t)(kNumTimeBins + 1);
   }
 };
 
@@ -286,20 +325,22 @@ struct LoopState<LOOP_LIMITER, T> {
   T hig2;
   int* wake;
   const int* perm;
-  __device__ __forceinline__ void load_i(const SoA& a, int i, T, const unsigned int* wake_words) {
-    const double4 p = a.pos[i];
-    const T hi = (T)p.w;
-    self = i;
+  template <typename Ix>
+  __device__ __forceinline__ void load_i(const SoA& a, Ix i, T, const unsigned int* wake_words,
+                                         bool = false) {
+    const PosRec p = a.pos[i];
+    const T hi = (T)h_of(p);
+    self = (int)i;
     n = 0;
     tbi = a.tb[i];
     n_owned = a.n_owned;
     hig2 = hi * hi * (T)kGamma2;
-    reach = p.w * (double)kGamma;
+    reach = (double)h_of(p) * (double)kGamma;
     // (writable device memory of the space, typed as the other loops' read-only array)
     wake = reinterpret_cast<int*>(const_cast<unsigned int*>(wake_words));
     perm = a.perm;
   }
-  __device__ __forceinline__ bool accept(int j, const double4&, T r2) const {
+  __device__ __forceinline__ bool accept(int j, const PosRec&, T r2) const {
     return (r2 < hig2) & (j != self);
   }
   __device__ __forceinline__ void wake_up(int j, int tbj) {
@@ -313,23 +354,26 @@ struct LoopState<LOOP_LIMITER, T> {
     if (__hip_atomic_load(&wake[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < -tbi)
       atomicMax(&wake[j], -tbi);
   }
-  __device__ __forceinline__ void interact(const SoA& a, int j, const double4&, T, T, T, T) {
+  __device__ __forceinline__ void interact(const SoA& a, int j, const PosRec&, T, T, T, T) {
     wake_up(j, a.tb[j]);
   }
   static constexpr int kPay = 1;  // walked four entries at a time, as density
   template <bool O32 = false>
-  __device__ static __forceinline__ JRec<1> load_j(const SoA& a, int j) {
+  __device__ static __forceinline__ JRec<1> load_j(const SoA& a, int j, const PosRec& pj) {
     JRec<1> r;
     // the record carries the entry's index (the scatter's target), no field
     r.p[0] = make_float4(__int_as_float(j), 0.f, 0.f, 0.f);
+    // (the bin from tb[j], not from the record: this walk reads only x, y, z of
+    // a position, 24 of its 32 bytes, and ran 3% slower fetching the rest)
     r.meta = a.tb[j];
     return r;
   }
-  __device__ __forceinline__ void interact_staged(const float4* p, int tbj, const double4&, T, T,
+  __device__ __forceinline__ void interact_staged(const float4* p, int tbj, const PosRec&, T, T,
                                                   T, T) {
     wake_up(__float_as_int(p[0].x), tbj);
   }
-  __device__ __forceinline__ void store(SoA&, int) const {}
+  __device__ __forceinline__ void store(SoA&, int, bool = false) const {}
+  __device__ static __forceinline__ void store_init(SoA&, int) {}  // (never fused)
 };
 
 // Grid-cell range of one particle: cells overlapping [x - R, x + R] per
@@ -381,8 +425,8 @@ __device__ __forceinline__ int wrap_cell(const GridDev& g, const CellRange& c, i
 
 // Separation x_i - x_j of candidate j under the row's image shifts.
 template <typename T>
-__device__ __forceinline__ T separation(const GridDev& g, const CellRange& c, const double4& pi,
-                                        const double4& pj, double sx, double sy, double sz,
+__device__ __forceinline__ T separation(const GridDev& g, const CellRange& c, const PosRec& pi,
+                                        const PosRec& pj, double sx, double sy, double sz,
                                         T& tdx, T& tdy, T& tdz) {
   double dx = pi.x - (pj.x + sx);
   double dy = pi.y - (pj.y + sy);

@@ -86,11 +86,11 @@ __global__ __launch_bounds__(256) void group_prep_kernel(
   box_init(b);
   for (int k = r; k < gr.y; k += 16) {
     const int i = gr.x + k;
-    const double4 p = a.pos[i];
+    const PosRec p = a.pos[i];
     const int pc = pcell[i];
     posf[i] = pc >= 0 ? cell_local(g, p, pc) : make_float4(0.f, 0.f, 0.f, 0.f);
     if (xd0) xd0[i] = xdiff[i];
-    if (active_part(a, i, max_active_bin)) box_add(b, p, p.w * (double)kGamma * gs1);
+    if (active_part(a, i, max_active_bin)) box_add(b, p, (double)h_of(p) * (double)kGamma * gs1);
   }
   for (int o = 8; o > 0; o >>= 1) {
     for (int d = 0; d < 3; d++) {
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void list_check_kernel(SoA a, ListDev ld, int6
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     if (a.tb[i] == kTimeBinInhibited || pcell[i] < 0) continue;
-    const double H = a.pos[i].w * (double)kGamma;
+    const double H = (double)h_of(a.pos[i]) * (double)kGamma;
     if (H + 2. * D > (double)ld.posf[i].w * gs1) bad = 1.f;
     if (!active_part(a, i, max_active_bin)) continue;
     if (ld.base[i] < 0 || H + 2. * D > (double)ld.reach[i]) bad = 1.f;
@@ -206,15 +206,17 @@ void walk_kernel(GridDev g, SoA a, ListDev ld, int i0, int n,
                                                    int max_active_bin, T a2H,
                                                    const unsigned int* __restrict__ hmax_bits,
                                                    unsigned long long* counter,
-                                                   int* __restrict__ ncount) {
+                                                   int* __restrict__ ncount, int fused) {
   list_walk<LOOP, T, kWalkLpi, O32>(g, a, ld, i0, n, max_active_bin, a2H, hmax_bits, counter,
-                                     ncount);
+                                     ncount, fused);
 }
 
 // The density walk held to 4 waves/SIMD (its four entries in flight per lane
 // want 132 VGPRs, i.e. 3 waves; at <= 128 it runs 1.157 -> 1.10 ms per loop
 // at 128^3; the force walk already fits 128 and does not gain).
-template <typename T>
+// FUSED: the pending init folded in (list_walk), at compile time: the kernel
+// has no register to spare for a run-time flag.
+template <typename T, bool FUSED>
 __global__ __launch_bounds__(kWalkBlock)
 #if SWH_WALK_WPE_DENS > 0
 __attribute__((amdgpu_waves_per_eu(SWH_WALK_WPE_DENS)))
@@ -222,8 +224,8 @@ __attribute__((amdgpu_waves_per_eu(SWH_WALK_WPE_DENS)))
 void density_walk_kernel(GridDev g, SoA a, ListDev ld, int i0, int n, int max_active_bin, T a2H,
                          const unsigned int* __restrict__ hmax_bits, unsigned long long* counter,
                          int* __restrict__ ncount) {
-  list_walk<LOOP_DENSITY, T, kWalkLpi>(g, a, ld, i0, n, max_active_bin, a2H, hmax_bits, counter,
-                                       ncount);
+  list_walk<LOOP_DENSITY, T, kWalkLpi, false, FUSED ? 1 : 0>(g, a, ld, i0, n, max_active_bin, a2H,
+                                                             hmax_bits, counter, ncount, 0);
 }
 
 // The list's overflow particles (more than K hits: a large H in a dense
@@ -231,8 +233,9 @@ void density_walk_kernel(GridDev g, SoA a, ListDev ld, int i0, int n, int max_ac
 // striding over each cell's particles, cells farther than max(H_i, the
 // cell's own max H) (force) or H_i (density, gradient) skipped; the lane
 // partial sums are combined at the end. The count is read on the device, so
-// the launch needs no host round trip.
-template <int LOOP, typename T>
+// the launch needs no host round trip. FUSED: as list_walk's fused (at compile
+// time: the plain search stays the code it was).
+template <int LOOP, typename T, bool FUSED = false>
 __global__ __launch_bounds__(256) void overflow_kernel(GridDev g, SoA a, ListDev ld,
                                                        const int* __restrict__ queue,
                                                        const unsigned int* __restrict__ qn,
@@ -248,9 +251,9 @@ __global__ __launch_bounds__(256) void overflow_kernel(GridDev g, SoA a, ListDev
     if (!active_part(a, i, max_active_bin)) continue;  // wave-uniform
     LoopState<LOOP, T> st;
     st.n = 0;
-    st.load_i(a, i, a2H, hmax_bits);
-    const double4 pi = a.pos[i];
-    const double Hi = pi.w * (double)kGamma;
+    st.load_i(a, i, a2H, hmax_bits, FUSED);
+    const PosRec pi = a.pos[i];
+    const double Hi = (double)h_of(pi) * (double)kGamma;
     CellRange c;
     cell_range(g, pi.x, pi.y, pi.z, st.reach, c);
     // The cells of the range are tested 64 at a time, one per lane (a large
@@ -292,7 +295,7 @@ __global__ __launch_bounds__(256) void overflow_kernel(GridDev g, SoA a, ListDev
         const int j0 = __shfl(r.x, b), j1 = __shfl(r.y, b);
         const double bx = __shfl(sx, b), by = __shfl(sy, b), bz = __shfl(sz, b);
         for (int j = j0 + lane; j < j1; j += 64) {
-          const double4 pj = a.pos[j];
+          const PosRec pj = a.pos[j];
           T dx, dy, dz;
           const T r2 = separation<T>(g, c, pi, pj, bx, by, bz, dx, dy, dz);
           if (st.accept(j, pj, r2)) st.interact(a, j, pj, dx, dy, dz, r2);
@@ -301,7 +304,7 @@ __global__ __launch_bounds__(256) void overflow_kernel(GridDev g, SoA a, ListDev
     }
     reduce_lanes<64, T>(st);
     if (lane == 0) {
-      st.store(a, i);
+      st.store(a, i, FUSED);
       if (ncount) ncount[i] = st.n;
       if (counter) atomicAdd(counter_stripe(counter), (unsigned long long)st.n);
     }
@@ -366,7 +369,7 @@ void walk_subset_kernel(GridDev g, SoA a, ListDev ld,
   const int i = t < nitems ? seg_at(subset, t) : -1;
   bool act = i >= 0 && active_part(a, i, max_active_bin);
   int nl = 0, lb = -1;
-  double4 pi = make_double4(0., 0., 0., 0.);
+  PosRec pi = PosRec{};
   bool search = false;
   if (act) {
     pi = a.pos[i];
@@ -375,7 +378,7 @@ void walk_subset_kernel(GridDev g, SoA a, ListDev ld,
       lb = ld.base[i];
     }
     const bool listed = list_ok && lb >= 0 && nl <= ld.K &&
-                        pi.w * (double)kGamma <= (double)ld.reach[i];
+                        (double)h_of(pi) * (double)kGamma <= (double)ld.reach[i];
     if (!listed) {
       search = true;
       act = false;
@@ -432,8 +435,8 @@ __device__ __forceinline__ void ghost_part(SoA& a, int i, bool first, float* lef
                                            const GhostParams& gp,
                                            const float* __restrict__ list_reach, bool& redo_out,
                                            float& hf_out, bool& stale) {
-  double4 pos = a.pos[i];
-  const T h_old = (T)(float)pos.w;
+  PosRec pos = a.pos[i];
+  const T h_old = (T)h_of(pos);
   const T h_old_dim = h_old * h_old * h_old;
   const T h_old_dim_minus_one = h_old * h_old;
   float4 th = a.th[i];
@@ -505,7 +508,7 @@ __device__ __forceinline__ void ghost_part(SoA& a, int i, bool first, float* lef
     const float hf = (float)hset;
     if (hf < gp.h_max && hf > gp.h_min) {
       // redo: store h, re-initialise (hydro_init_part), queue for the rerun
-      pos.w = (double)hf;
+      pos.h = hf;
       a.pos[i] = pos;
       th.y = 0.f;
       a.th[i] = th;  // (a whole-record store, not a 4-byte one into it)
@@ -534,7 +537,7 @@ __device__ __forceinline__ void ghost_part(SoA& a, int i, bool first, float* lef
     }
   }
   const float hf = (float)h_final;
-  pos.w = (double)hf;
+  pos.h = hf;
   a.pos[i] = pos;
   hf_out = hf;
   // the step's pair lists cover this particle's loops only while H <= its R
@@ -648,8 +651,8 @@ __global__ __launch_bounds__(256) void grown_mark_kernel(GridDev g, SoA a, ListD
   };
   if (lane == 0) queue(j);
   if (!force) return;
-  const double4 pj = a.pos[j];
-  const double Hj = pj.w * (double)kGamma;
+  const PosRec pj = a.pos[j];
+  const double Hj = (double)h_of(pj) * (double)kGamma;
   // the per-cell reach the force searches prune by (adaptive grid) must
   // cover the grown H too
   if (cell_R && lane == 0 && pcell[j] >= 0)
@@ -700,7 +703,7 @@ __global__ void extra_ghost_kernel(SoA a, int64_t n, int max_active_bin, ForcePr
   if (i >= n) return;
   const int tb = a.tb[i];
   if (!active_part(a, i, max_active_bin)) return;
-  const T h = (T)(float)a.pos[i].w;
+  const T h = (T)h_of(a.pos[i]);
   const T h_inv = (T)1 / h;
   const T h_inv_dim = h_inv * h_inv * h_inv;
   const T h_inv_dim_plus_one = h_inv_dim * h_inv;
@@ -771,7 +774,7 @@ __global__ void reset_acc_kernel(SoA a, int64_t n, int max_active_bin) {
 __global__ void end_force_kernel(SoA a, int64_t n, int max_active_bin) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || !active_part(a, i, max_active_bin)) return;
-  a.hdt[i] = a.hdt[i] * ((float)a.pos[i].w * kDimInv);  // hydro.h:1080-1084
+  a.hdt[i] = a.hdt[i] * (h_of(a.pos[i]) * kDimInv);  // hydro.h:1080-1084
 }
 
 // ---------------------------------------------------------------------------
@@ -890,7 +893,7 @@ static swh_status build_lists(swh_space* s, const swh_hydro_params* P, bool coun
                        s->stream, s->cell_hreach.as<unsigned int>(), (int64_t)s->grid.ncell,
                        run_if);
     hipLaunchKernelGGL(cell_reach_kernel, dim3((int)((s->n + 255) / 256)), dim3(256), 0,
-                       s->stream, s->pos.as<const double4>(), s->pcell.as<const int>(), s->n,
+                       s->stream, s->pos.as<const PosRec>(), s->pcell.as<const int>(), s->n,
                        (float)(kGamma * ld.skin1), s->cell_hreach.as<unsigned int>(), run_if);
   }
   SWH_TRY(s->gplan.reserve((size_t)std::max(1, s->ngroups) * sizeof(BuildPlan)));
@@ -939,7 +942,7 @@ static swh_status check_kept_lists(swh_space* s, const swh_hydro_params* P, bool
 // (pos, 32 B per particle) must end below 2^32 bytes; a larger space walks
 // with plain 64-bit indexing.
 static bool walk_off32(const swh_space* s) {
-  return (unsigned long long)s->n * sizeof(double4) < (1ull << 32);
+  return (unsigned long long)s->n * sizeof(PosRec) < (1ull << 32);
 }
 
 // The auxiliary device array a loop's states get (load_i's last argument): max
@@ -952,7 +955,7 @@ static const unsigned int* loop_aux(swh_space* s) {
 template <int LOOP, typename T>
 static void launch_typed(swh_space* s, const GridDev& gd, const SegList* subset, int nitems,
                          int max_active_bin, T a2H, unsigned long long* ctr, int* ncount,
-                         const unsigned int* mark = nullptr) {
+                         const unsigned int* mark = nullptr, int fused = 0) {
   const int block = 256;
   ListDev ld = list_dev(s);
   ld.mark = mark;
@@ -972,26 +975,39 @@ static void launch_typed(swh_space* s, const GridDev& gd, const SegList* subset,
     return;
   }
   constexpr int wppb = kWalkBlock / kWalkLpi;
-  if (LOOP == LOOP_DENSITY && sizeof(T) == 8)  // (the fp32 walk would spill)
-    hipLaunchKernelGGL((density_walk_kernel<T>), dim3((nitems + wppb - 1) / wppb),
+  if (LOOP == LOOP_DENSITY && sizeof(T) == 8 && fused)  // (the fp32 walk would spill)
+    hipLaunchKernelGGL((density_walk_kernel<T, true>), dim3((nitems + wppb - 1) / wppb),
+                       dim3(kWalkBlock), 0, s->stream, gd, soa_of(s), ld, 0, nitems,
+                       max_active_bin, a2H, hmax_slot(s), ctr, ncount);
+  else if (LOOP == LOOP_DENSITY && sizeof(T) == 8)
+    hipLaunchKernelGGL((density_walk_kernel<T, false>), dim3((nitems + wppb - 1) / wppb),
                        dim3(kWalkBlock), 0, s->stream, gd, soa_of(s), ld, 0, nitems,
                        max_active_bin, a2H, hmax_slot(s), ctr, ncount);
   else if (LOOP == LOOP_FORCE && walk_off32(s))
     hipLaunchKernelGGL((walk_kernel<LOOP, T, LOOP == LOOP_FORCE>), dim3((nitems + wppb - 1) / wppb),
                        dim3(kWalkBlock), 0, s->stream, gd, soa_of(s), ld, 0, nitems,
-                       max_active_bin, a2H, hmax_slot(s), ctr, ncount);
+                       max_active_bin, a2H, hmax_slot(s), ctr, ncount, fused);
   else
     hipLaunchKernelGGL((walk_kernel<LOOP, T, false>), dim3((nitems + wppb - 1) / wppb),
                        dim3(kWalkBlock), 0, s->stream, gd, soa_of(s), ld, 0, nitems,
-                       max_active_bin, a2H, loop_aux<LOOP>(s), ctr, ncount);
+                       max_active_bin, a2H, loop_aux<LOOP>(s), ctr, ncount, fused);
+  if constexpr (LOOP == LOOP_DENSITY || LOOP == LOOP_FORCE) {
+    if (fused) {
+      hipLaunchKernelGGL((overflow_kernel<LOOP, T, true>), dim3(64), dim3(block), 0, s->stream, gd,
+                         soa_of(s), ld, ld.ovf, ld.ovf_n, max_active_bin, a2H, loop_aux<LOOP>(s),
+                         ctr, ncount);
+      return;
+    }
+  }
   hipLaunchKernelGGL((overflow_kernel<LOOP, T>), dim3(64), dim3(block), 0, s->stream, gd,
                      soa_of(s), ld, ld.ovf, ld.ovf_n, max_active_bin, a2H, loop_aux<LOOP>(s), ctr,
                      ncount);
 }
 
+// fused: the loop takes over the pending init / reset (pending_take)
 template <int LOOP>
 static swh_status launch_loop(swh_space* s, const swh_hydro_params* P, const SegList* subset,
-                              int nitems, bool count) {
+                              int nitems, bool count, int fused = 0) {
   if (nitems <= 0) return SWH_OK;
   if (!subset && s->ngroups <= 0) return SWH_OK;
   if (!subset) {
@@ -1043,10 +1059,11 @@ static swh_status launch_loop(swh_space* s, const swh_hydro_params* P, const Seg
                        s->grown_search.as<int>(), qn);
   }
   if (f64)
-    launch_typed<LOOP, double>(s, gd, subset, nitems, P->max_active_bin, a2H, ctr, ncount, mark);
+    launch_typed<LOOP, double>(s, gd, subset, nitems, P->max_active_bin, a2H, ctr, ncount, mark,
+                               fused);
   else
     launch_typed<LOOP, float>(s, gd, subset, nitems, P->max_active_bin, (float)a2H, ctr,
-                              ncount, mark);
+                              ncount, mark, fused);
   if (grown) {
     const ListDev ld = list_dev(s);
     const int* q = s->grown_search.as<const int>();
@@ -1064,6 +1081,30 @@ static swh_status launch_loop(swh_space* s, const swh_hydro_params* P, const Seg
   return SWH_OK;
 }
 
+// The pending init / reset at the start of a full-set loop: the density loop
+// takes over a pending init, the force loop a pending reset (*fused = 1: the
+// stores write their sums; nothing is launched for the operation), provided it
+// was recorded for the loop's max_active_bin and the loop writes every active
+// particle exactly once, from the walk or from the list-overflow search: a
+// plain run (no profiling mode that ends after the build or alters the
+// walks), with i-groups, and no ghost-grown set, whose particles a third
+// launch would write. Anything else is applied first with its own kernel.
+#ifndef SWH_FOLD_PENDING  // (A/B switch: 0 applies every pending operation with its kernel)
+#define SWH_FOLD_PENDING 1
+#endif
+template <int LOOP>
+static swh_status pending_take(swh_space* s, const swh_hydro_params* P, int* fused) {
+  *fused = 0;
+  if (s->pending_op == PENDING_NONE) return SWH_OK;
+  const int mine = LOOP == LOOP_DENSITY ? PENDING_INIT : LOOP == LOOP_FORCE ? PENDING_RESET : -1;
+  if (!SWH_FOLD_PENDING || s->pending_op != mine || s->pending_mab != P->max_active_bin || s->tuning.diag_mode != 0 ||
+      s->ngroups <= 0 || s->grown_n != 0)
+    return space_apply_pending(s);
+  s->pending_op = PENDING_NONE;
+  *fused = 1;
+  return SWH_OK;
+}
+
 template <int LOOP>
 static swh_status run_loop(swh_space* s, const swh_hydro_params* P, int64_t* n_out) {
   SWH_TRY(check_built(s));
@@ -1073,6 +1114,8 @@ static swh_status run_loop(swh_space* s, const swh_hydro_params* P, int64_t* n_o
     return SWH_OK;
   }
   SWH_HIP(hipSetDevice(s->ctx->device));
+  int fused = 0;
+  SWH_TRY(pending_take<LOOP>(s, P, &fused));
   // counted launch: slot 0 = interactions, 3 = list entries, 4-7 = work counters
   unsigned long long* ctr = counter_slot(s);
   if (n_out) SWH_HIP(hipMemsetAsync(ctr + 3, 0, 5 * sizeof(unsigned long long), s->stream));
@@ -1081,7 +1124,13 @@ static swh_status run_loop(swh_space* s, const swh_hydro_params* P, int64_t* n_o
                     s->list_mab == P->max_active_bin;
   const bool fresh = s->list_valid && s->list_mab == P->max_active_bin;
   const bool rebuilds = (LOOP == LOOP_DENSITY && !(keep && fresh)) || !fresh;
-  SWH_TRY(launch_loop<LOOP>(s, P, nullptr, (int)s->n, n_out != nullptr));
+  const swh_status launched = launch_loop<LOOP>(s, P, nullptr, (int)s->n, n_out != nullptr, fused);
+  if (launched != SWH_OK) {
+    // the loop that took the pending operation over did not run (its launches
+    // come last, behind everything that can fail): it is pending again
+    if (fused) s->pending_op = LOOP == LOOP_DENSITY ? PENDING_INIT : PENDING_RESET;
+    return launched;
+  }
   if (n_out) {
     unsigned long long* stripes = nullptr;
     SWH_TRY(stripes_slot(s, &stripes));
@@ -1110,12 +1159,46 @@ static swh_status run_loop(swh_space* s, const swh_hydro_params* P, int64_t* n_o
 // no valid lists (after swh_space_timestep dropped them) it builds them for
 // the starting set first.
 swh_status space_limiter_walk(swh_space* s, const swh_hydro_params* P) {
+  SWH_TRY(space_apply_pending(s));
   SWH_TRY(check_built(s));
   if (!s->wake_sorted) {
     set_error("the limiter walk needs the wake-up words in sorted order");
     return SWH_ERR_STATE;
   }
   return launch_loop<LOOP_LIMITER>(s, P, nullptr, (int)s->n, false);
+}
+
+swh_status space_apply_pending(swh_space* s) {
+  if (!s || s->pending_op == PENDING_NONE) return SWH_OK;
+  const int op = s->pending_op;
+  if (s->n == 0) {
+    s->pending_op = PENDING_NONE;
+    return SWH_OK;
+  }
+  SWH_HIP(hipSetDevice(s->ctx->device));
+  const int block = 256;
+  const dim3 grid((int)((s->n + block - 1) / block));
+  if (op == PENDING_INIT)
+    hipLaunchKernelGGL(init_kernel, grid, dim3(block), 0, s->stream, soa_of(s), s->n,
+                       s->pending_mab);
+  else
+    hipLaunchKernelGGL(reset_acc_kernel, grid, dim3(block), 0, s->stream, soa_of(s), s->n,
+                       s->pending_mab);
+  SWH_HIP(hipGetLastError());
+  s->pending_op = PENDING_NONE;  // (only once it is launched: a failure above leaves it recorded)
+  return SWH_OK;
+}
+
+// Record an init / reset for the next loop (pending_take); one already
+// recorded for the same set stands (both are idempotent).
+static swh_status pending_record(swh_space* s, const swh_hydro_params* P, int op) {
+  if (!s || !P) return SWH_ERR_ARG;
+  if (s->pending_op == op && s->pending_mab == P->max_active_bin) return SWH_OK;
+  SWH_TRY(space_apply_pending(s));
+  if (s->n == 0) return SWH_OK;
+  s->pending_op = op;
+  s->pending_mab = P->max_active_bin;
+  return SWH_OK;
 }
 
 }  // namespace swh
@@ -1125,14 +1208,7 @@ using namespace swh;
 extern "C" {
 
 swh_status swh_space_init_parts(swh_space* s, const swh_hydro_params* P) {
-  if (!s || !P) return SWH_ERR_ARG;
-  if (s->n == 0) return SWH_OK;
-  SWH_HIP(hipSetDevice(s->ctx->device));
-  const int block = 256;
-  hipLaunchKernelGGL(init_kernel, dim3((int)((s->n + block - 1) / block)), dim3(block), 0,
-                     s->stream, soa_of(s), s->n, P->max_active_bin);
-  SWH_HIP(hipGetLastError());
-  return SWH_OK;
+  return pending_record(s, P, PENDING_INIT);
 }
 
 swh_status swh_density_loop(swh_space* s, const swh_hydro_params* P, int64_t* n) {
@@ -1147,6 +1223,7 @@ swh_status swh_force_loop(swh_space* s, const swh_hydro_params* P, int64_t* n) {
 
 swh_status swh_ghost(swh_space* s, const swh_hydro_params* P, int32_t* iterations,
                      int64_t* n_unconverged) {
+  SWH_TRY(space_apply_pending(s));
   SWH_TRY(check_built(s));
   if (!P) return SWH_ERR_ARG;
   if (iterations) *iterations = 0;
@@ -1336,6 +1413,7 @@ swh_status swh_ghost(swh_space* s, const swh_hydro_params* P, int32_t* iteration
 }
 
 swh_status swh_extra_ghost(swh_space* s, const swh_hydro_params* P) {
+  SWH_TRY(space_apply_pending(s));
   SWH_TRY(check_built(s));
   if (!P) return SWH_ERR_ARG;
   if (s->n == 0) return SWH_OK;
@@ -1366,17 +1444,11 @@ swh_status swh_extra_ghost(swh_space* s, const swh_hydro_params* P) {
 }
 
 swh_status swh_space_reset_acceleration(swh_space* s, const swh_hydro_params* P) {
-  if (!s || !P) return SWH_ERR_ARG;
-  if (s->n == 0) return SWH_OK;
-  SWH_HIP(hipSetDevice(s->ctx->device));
-  const int block = 256;
-  hipLaunchKernelGGL(reset_acc_kernel, dim3((int)((s->n + block - 1) / block)), dim3(block),
-                     0, s->stream, soa_of(s), s->n, P->max_active_bin);
-  SWH_HIP(hipGetLastError());
-  return SWH_OK;
+  return pending_record(s, P, PENDING_RESET);
 }
 
 swh_status swh_end_force(swh_space* s, const swh_hydro_params* P) {
+  SWH_TRY(space_apply_pending(s));
   SWH_TRY(check_built(s));
   if (!P) return SWH_ERR_ARG;
   if (s->n == 0) return SWH_OK;

@@ -233,7 +233,7 @@ struct swh_space {
   swh::Layout layout{};
 
   // sorted SoA (j-records packed for gathers)
-  swh::DevBuf pos;   // double4 x,y,z,h
+  swh::DevBuf pos;   // PosRec x,y,z,h + time bin (swh_space.h)
   swh::DevBuf vm;    // float4 vx,vy,vz,m
   swh::DevBuf th;    // float4 u,rho,P,c
   swh::DevBuf fc;    // float4 f,balsara,alpha_visc,alpha_diff
@@ -328,7 +328,19 @@ struct swh_space {
   swh::HostBuf ghost_host;  // pinned: the passes' counts read back
   unsigned int* ghost_zero_next = nullptr;  // cleared by the rerun launch (swh_ghost)
   swh::HostBuf hstage;
+  // A recorded, not yet launched swh_space_init_parts / _reset_acceleration
+  // (swh::PendingOp) and its max_active_bin. The matching full-set loop folds
+  // it into its stores; any other entry applies it first (space_apply_pending).
+  int32_t pending_op = 0, pending_mab = 0;
 };
+
+namespace swh {
+enum PendingOp { PENDING_NONE = 0, PENDING_INIT = 1, PENDING_RESET = 2 };
+// swh_hydro.hip: launch the recorded init / reset on the space's stream. Every
+// exported entry that can read or write a space's particle fields starts
+// with it (the loop that folds the operation in takes it over instead).
+swh_status space_apply_pending(swh_space* s);
+}  // namespace swh
 
 struct swh_gspace {
   swh_context* ctx = nullptr;

@@ -198,12 +198,13 @@ __global__ __launch_bounds__(256) void step_kernel(SoA a, float4* __restrict__ v
         long long ti_end, ti_beg;
         if (bin <= T.max_active_bin) {
           bool below;
-          const float new_dt = part_timestep<LK>(T, (float)a.pos[s].w, a.grad[s].x, a.hdt[s], ac,
+          const float new_dt = part_timestep<LK>(T, h_of(a.pos[s]), a.grad[s].x, a.hdt[s], ac,
                                                  ag, hg, &below, gm);
           const int64_t new_dti =
               make_integer_timestep(new_dt, bin, a.mintb[s], T.ti_current, T.time_base_inv);
           bin = get_time_bin(new_dti);
           a.tb[s] = (int8_t)bin;
+          set_bin(a.pos[s], bin);  // (the copy the walks gather)
           n_updated++;
           n_below += below ? 1u : 0u;
           ti_end = T.ti_current + new_dti;
@@ -396,38 +397,45 @@ using namespace swh;
 extern "C" {
 
 swh_status swh_space_kick1(swh_space* s, const swh_kick_params* K, const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   return launch_step<false, false, true>(s, nullptr, nullptr, K, P, "swh_space_kick1");
 }
 
 swh_status swh_space_kick2(swh_space* s, const swh_kick_params* K, const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   return launch_step<true, false, false>(s, K, nullptr, nullptr, P, "swh_space_kick2");
 }
 
 swh_status swh_space_timestep(swh_space* s, const swh_timestep_params* T,
                               const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   return launch_step<false, true, false>(s, nullptr, T, nullptr, P, "swh_space_timestep");
 }
 
 swh_status swh_space_end_step(swh_space* s, const swh_kick_params* K2,
                               const swh_timestep_params* T, const swh_kick_params* K1,
                               const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   return launch_step<true, true, true>(s, K2, T, K1, P, "swh_space_end_step");
 }
 
 swh_status swh_space_kick1_linked(swh_space* s, const swh_kick_params* K,
                                   const swh_hydro_params* P, double dt_kick_mesh_grav) {
+  SWH_TRY(swh::space_apply_pending(s));
   return launch_step<false, false, true, true>(s, nullptr, nullptr, K, P,
                                                "swh_space_kick1_linked", 0., dt_kick_mesh_grav);
 }
 
 swh_status swh_space_kick2_linked(swh_space* s, const swh_kick_params* K,
                                   const swh_hydro_params* P, double dt_kick_mesh_grav) {
+  SWH_TRY(swh::space_apply_pending(s));
   return launch_step<true, false, false, true>(s, K, nullptr, nullptr, P,
                                                "swh_space_kick2_linked", dt_kick_mesh_grav, 0.);
 }
 
 swh_status swh_space_timestep_linked(swh_space* s, const swh_timestep_params* T,
                                      const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   return launch_step<false, true, false, true>(s, nullptr, T, nullptr, P,
                                                "swh_space_timestep_linked");
 }
@@ -436,11 +444,13 @@ swh_status swh_space_end_step_linked(swh_space* s, const swh_kick_params* K2,
                                      const swh_timestep_params* T, const swh_kick_params* K1,
                                      const swh_hydro_params* P, double dt_kick_mesh2,
                                      double dt_kick_mesh1) {
+  SWH_TRY(swh::space_apply_pending(s));
   return launch_step<true, true, true, true>(s, K2, T, K1, P, "swh_space_end_step_linked",
                                              dt_kick_mesh2, dt_kick_mesh1);
 }
 
 swh_status swh_space_step_result(swh_space* s, swh_step_result* out) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || !out) return SWH_ERR_ARG;
   if (!s->step.has_ts) {
     set_error("swh_space_timestep or swh_space_end_step must precede swh_space_step_result");
@@ -453,6 +463,7 @@ swh_status swh_space_step_result(swh_space* s, swh_step_result* out) {
 
 swh_status swh_space_download_xparts(swh_space* s, void* xparts, const swh_xpart_layout* XL,
                                      int on_device) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || !XL || (s->n > 0 && !xparts) || XL->stride <= 0 || XL->off_v_full < 0 ||
       XL->off_v_full + 12 > XL->stride || XL->off_u_full + 4 > XL->stride) {
     set_error("xpart layout must hold v_full (and u_full, if given) inside the record");
@@ -481,6 +492,7 @@ swh_status swh_space_download_xparts(swh_space* s, void* xparts, const swh_xpart
 }
 
 swh_status swh_space_upload_a_grav(swh_space* s, const float* a_grav, int on_device) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || (s->n > 0 && !a_grav)) return SWH_ERR_ARG;
   if (s->n == 0) return SWH_OK;
   if (!s->xparts_valid) {

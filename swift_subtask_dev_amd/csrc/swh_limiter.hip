@@ -122,6 +122,7 @@ __global__ __launch_bounds__(256) void limiter_apply_kernel(
     float u_full = vf.w, u_dt = ac.w;
     const LimitedPart r = limiter_limit_part(K, bin, w, v, &u_full, &u_dt, ah, g3, hasg[s] != 0);
     a.tb[s] = (int8_t)r.new_bin;
+    set_bin(a.pos[s], r.new_bin);  // (the copy the walks gather)
     if (r.was_active) {
       n_act++;
     } else {
@@ -286,6 +287,7 @@ using namespace swh;
 extern "C" {
 
 swh_status swh_space_limiter_loop(swh_space* s, const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || !P) return SWH_ERR_ARG;
   SWH_TRY(not_linked(s, "swh_space_limiter_loop"));
   if (s->n == 0) return SWH_OK;
@@ -293,6 +295,7 @@ swh_status swh_space_limiter_loop(swh_space* s, const swh_hydro_params* P) {
 }
 
 swh_status swh_space_download_wakeup(swh_space* s, int8_t* out, int on_device) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || (s->n > 0 && !out)) return SWH_ERR_ARG;
   if (s->n == 0) return SWH_OK;
   SWH_HIP(hipSetDevice(s->ctx->device));
@@ -313,6 +316,7 @@ swh_status swh_space_download_wakeup(swh_space* s, int8_t* out, int on_device) {
 
 swh_status swh_space_limiter_apply(swh_space* s, const swh_limiter_params* L,
                                    const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || !L || !P) return SWH_ERR_ARG;
   SWH_TRY(not_linked(s, "swh_space_limiter_apply"));
   if (s->n == 0) return SWH_OK;
@@ -320,6 +324,7 @@ swh_status swh_space_limiter_apply(swh_space* s, const swh_limiter_params* L,
 }
 
 swh_status swh_space_limiter_loop_linked(swh_space* s, const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   const char* what = "swh_space_limiter_loop_linked";
   if (!s || !P) return SWH_ERR_ARG;
   SWH_TRY(need_link(s, what));
@@ -330,6 +335,7 @@ swh_status swh_space_limiter_loop_linked(swh_space* s, const swh_hydro_params* P
 
 swh_status swh_space_limiter_apply_linked(swh_space* s, const swh_limiter_params* L,
                                           const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   const char* what = "swh_space_limiter_apply_linked";
   if (!s || !L || !P) return SWH_ERR_ARG;
   SWH_TRY(need_link(s, what));
@@ -344,6 +350,7 @@ swh_status swh_space_end_step_limited_linked(swh_space* s, const swh_kick_params
                                              const swh_limiter_params* L,
                                              const swh_hydro_params* P, double dt_kick_mesh2,
                                              double dt_kick_mesh1) {
+  SWH_TRY(swh::space_apply_pending(s));
   const char* what = "swh_space_end_step_limited_linked";
   if (!s || !K2 || !T || !K1 || !L || !P) return SWH_ERR_ARG;
   SWH_TRY(need_link(s, what));
@@ -362,6 +369,7 @@ swh_status swh_space_end_step_limited_linked(swh_space* s, const swh_kick_params
 swh_status swh_space_end_step_limited(swh_space* s, const swh_kick_params* K2,
                                       const swh_timestep_params* T, const swh_kick_params* K1,
                                       const swh_limiter_params* L, const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   const char* what = "swh_space_end_step_limited";
   if (!s || !K2 || !T || !K1 || !L || !P) return SWH_ERR_ARG;
   SWH_TRY(not_linked(s, what));
@@ -378,6 +386,7 @@ swh_status swh_space_end_step_limited(swh_space* s, const swh_kick_params* K2,
 }
 
 swh_status swh_space_limiter_result(swh_space* s, swh_limiter_result* out) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || !out) return SWH_ERR_ARG;
   out->n_woken_active = out->n_woken_inactive = 0;
   out->min_new_bin = SWH_NUM_TIME_BINS + 1;

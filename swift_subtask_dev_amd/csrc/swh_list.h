@@ -126,7 +126,7 @@ __device__ __forceinline__ void box_init(GroupBox& b) {
   b.Rg = 0.;
   b.pad = 0.;
 }
-__device__ __forceinline__ void box_add(GroupBox& b, const double4& p, double R) {
+__device__ __forceinline__ void box_add(GroupBox& b, const PosRec& p, double R) {
   b.lo[0] = p.x < b.lo[0] ? p.x : b.lo[0];
   b.lo[1] = p.y < b.lo[1] ? p.y : b.lo[1];
   b.lo[2] = p.z < b.lo[2] ? p.z : b.lo[2];
@@ -189,7 +189,7 @@ __device__ __forceinline__ void build_plan(const GridDev& g, const GroupBox& b, 
 // rebuild): after a drift it may stand outside that cell's box, and the build
 // stages it from there (the box gaps allow for g.dx); inhibited particles
 // (pcell < 0) are in no cell.
-__global__ void cell_reach_kernel(const double4* __restrict__ pos, const int* __restrict__ pcell,
+__global__ void cell_reach_kernel(const PosRec* __restrict__ pos, const int* __restrict__ pcell,
                                   int64_t n, float gs1, unsigned int* __restrict__ cell_R,
                                   const unsigned int* run_if) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -197,7 +197,7 @@ __global__ void cell_reach_kernel(const double4* __restrict__ pos, const int* __
   const int lin = pcell[j];
   if (lin < 0) return;
   // positive floats order as their bit patterns
-  atomicMax(&cell_R[lin], __float_as_uint((float)(pos[j].w * (double)gs1) * 1.0000005f));
+  atomicMax(&cell_R[lin], __float_as_uint((float)((double)h_of(pos[j]) * (double)gs1) * 1.0000005f));
 }
 
 // Candidates per lane per staging pass. Two: a 256-slot region then takes
@@ -261,13 +261,13 @@ __device__ __forceinline__ int wave_incl_max(int v) {
 // The cell is the particle's sorted cell (pcell, from the rebuild), not the
 // one its current position falls in: after a drift the offset may leave
 // [0, w) by up to g.dx, and staging adds the sorted cell's corner back.
-__device__ __forceinline__ float4 cell_local(const GridDev& g, const double4& p, int lin) {
+__device__ __forceinline__ float4 cell_local(const GridDev& g, const PosRec& p, int lin) {
   const double xs[3] = {p.x, p.y, p.z};
   const int ck[3] = {lin % g.cdim[0], (lin / g.cdim[0]) % g.cdim[1],
                      lin / (g.cdim[0] * g.cdim[1])};
   float l[3];
   for (int k = 0; k < 3; k++) l[k] = (float)(xs[k] - (g.origin[k] + ck[k] * g.w[k]));
-  return make_float4(l[0], l[1], l[2], (float)p.w);
+  return make_float4(l[0], l[1], l[2], h_of(p));
 }
 
 // Copy i's pending LDS hits to its global list (the LPI lanes of i split them).
@@ -473,7 +473,7 @@ struct BuildSlot {
   bool act;     // active i with a list
   int nl;       // its entries (> K: overflow)
   int lb;       // its list base (group * kListSlots + slot)
-  double4 pi;   // position, h
+  PosRec pi;   // position, h
 };
 
 // Build the pair lists of one i-group (one wave).
@@ -493,9 +493,9 @@ __device__ __forceinline__ BuildSlot list_build(const GridDev& g, const SoA& a, 
   const int i = il < gr.y ? gr.x + il : -1;
   const bool act = i >= 0 && active_part(a, i, max_active_bin);
   const double skin1 = (double)ld.skin1;
-  double4 pi = make_double4(0., 0., 0., 0.);
+  PosRec pi = PosRec{};
   if (act) pi = a.pos[i];
-  const double Ri = act ? pi.w * (double)kGamma * skin1 : 0.;
+  const double Ri = act ? (double)h_of(pi) * (double)kGamma * skin1 : 0.;
   // the group's build plan (wave-uniform: scalar loads)
   const BuildPlan& P = ld.plan[gid < ngroups ? gid : 0];
   const double Rg = gid < ngroups ? P.Rg : 0.;
@@ -699,7 +699,7 @@ __device__ __forceinline__ BuildSlot list_build(const GridDev& g, const SoA& a, 
 }
 
 // Does particle x need the nearest-image wrap (within R of a periodic face)?
-__device__ __forceinline__ bool near_face(const GridDev& g, const double4& p, double R) {
+__device__ __forceinline__ bool near_face(const GridDev& g, const PosRec& p, double R) {
   return (p.x < R) | (p.x > g.dim[0] - R) | (p.y < R) | (p.y > g.dim[1] - R) | (p.z < R) |
          (p.z > g.dim[2] - R);
 }
@@ -709,15 +709,18 @@ __device__ __forceinline__ bool near_face(const GridDev& g, const double4& p, do
 // window's is loaded ahead), then the four entries' particle data are loaded
 // together (only lanes that have them issue loads) and evaluated.
 // O32: the force walk's gathers use 32-bit byte offsets (gather_at).
-template <int LPI, bool WRAP, typename T, bool O32 = false, class S>
+// PRE: the caller has loaded the lane's first window (wv0 = walk_window0)
+// with the i-side records, so the two share one memory round trip.
+template <int LPI, bool WRAP, typename T, bool O32 = false, bool PRE = false, class S>
 __device__ __forceinline__ void walk_entries(const GridDev& g, const SoA& a, const ListDev& ld,
-                                             const double4& pi, int nl, int lb, int s, S& st) {
+                                             const PosRec& pi, int nl, int lb, int s, S& st,
+                                             const int4& wv0 = int4{0, 0, 0, 0}) {
   static_assert(LPI == kWalkLpi, "the list layout gives each walk lane of an i its own windows");
   const int nme = nl > s ? (nl - s + LPI - 1) / LPI : 0;  // this lane's entries
   const int nw = (nme + 3) >> 2;
   if (nw == 0) return;
   const int* __restrict__ lanep = ld.nbr + list_lane(lb, ld.KS) + s * 4;
-  auto step = [&](int j, const double4& pj, const JRec<S::kPay>& rj) {
+  auto step = [&](int j, const PosRec& pj, const JRec<S::kPay>& rj) {
     double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
     if (WRAP) {
       dx = wrap_nearest(dx, g.dim[0]);
@@ -728,7 +731,8 @@ __device__ __forceinline__ void walk_entries(const GridDev& g, const SoA& a, con
     const T r2 = tdx * tdx + tdy * tdy + tdz * tdz;
     if (st.accept(j, pj, r2)) st.interact_staged(rj.p, rj.meta, pj, tdx, tdy, tdz, r2);
   };
-  int4 wv = *reinterpret_cast<const int4*>(lanep);
+  int4 wv = wv0;
+  if constexpr (!PRE) wv = *reinterpret_cast<const int4*>(lanep);
   if constexpr (S::kPay > 1) {
     // heavy records (gradient, force): one entry at a time (one record live:
     // 4 waves/SIMD)
@@ -745,8 +749,8 @@ __device__ __forceinline__ void walk_entries(const GridDev& g, const SoA& a, con
           if (m + 4 < nme) wv = *reinterpret_cast<const int4*>(lanep + ((m >> 2) + 1) * kWinInts);
         }
         const int j = q == 0 ? cur.x : q == 1 ? cur.y : q == 2 ? cur.z : cur.w;
-        const double4 pj = a.pos[j];
-        const JRec<S::kPay> rj = S::load_j(a, j);
+        const PosRec pj = a.pos[j];
+        const JRec<S::kPay> rj = S::load_j(a, j, pj);
         step(j, pj, rj);
       }
       return;
@@ -764,8 +768,8 @@ __device__ __forceinline__ void walk_entries(const GridDev& g, const SoA& a, con
       const int q = m & 3;
       if (q == 0) cur = wv;
       const int j = q == 0 ? cur.x : q == 1 ? cur.y : q == 2 ? cur.z : cur.w;
-      const double4 pj = gather_at<O32>(a.pos, j);
-      const JRec<S::kPay> rj = S::template load_j<O32>(a, j);
+      const PosRec pj = gather_at<O32>(a.pos, j);
+      const JRec<S::kPay> rj = S::template load_j<O32>(a, j, pj);
       double dx = pi.x - pj.x, dy = pi.y - pj.y, dz = pi.z - pj.z;
       if (WRAP) {
         dx = wrap_nearest(dx, g.dim[0]);
@@ -786,13 +790,13 @@ __device__ __forceinline__ void walk_entries(const GridDev& g, const SoA& a, con
     if (w + 1 < nw) wv = *reinterpret_cast<const int4*>(lanep + (w + 1) * kWinInts);
     const int mrem = nme - 4 * w;  // entries of this window (>= 1)
     {
-      double4 pj[4];
+      PosRec pj[4];
       JRec<S::kPay> rj[4];
 #pragma unroll
       for (int q = 0; q < 4; q++) {
         if (q < mrem) {
           pj[q] = a.pos[jv[q]];
-          rj[q] = S::load_j(a, jv[q]);
+          rj[q] = S::load_j(a, jv[q], pj[q]);
         }
       }
 #pragma unroll
@@ -812,41 +816,102 @@ __device__ __forceinline__ void walk_entries(const GridDev& g, const SoA& a, con
 #endif
 constexpr int kWalkBlock = SWH_WALK_BLOCK;
 
-template <int LOOP, typename T, int LPI, bool O32 = false>
+// The first window of walk lane s of the list at base lb (walk_entries'
+// starting point). Every listed slot has it in memory (KS >= 4 WL), so the
+// caller loads it for any listed i, with or without entries.
+__device__ __forceinline__ int4 walk_window0(const ListDev& ld, int lb, int s) {
+  static_assert(list_ks(1) * kListSlots >= kWinInts, "a group's block holds a whole window row");
+  return *reinterpret_cast<const int4*>(ld.nbr + list_lane(lb, ld.KS) + s * 4);
+}
+
+// (A/B switch: 0 gives the force walk the other walks' prologue)
+#ifndef SWH_WALK_TWO_TRIP
+#define SWH_WALK_TWO_TRIP 1
+#endif
+
+// The force walk's wave starts with two memory round trips. The first brings
+// the small per-i words (time bin, owner, list length and base, the grown
+// mark) of every lane, issued together with no branch between them; the
+// activity test follows from them. The second brings, for the active lanes,
+// the i-side records and the list's first window (whose address needs only
+// the base). A wave with no active lane ends after the first: a sparse step
+// reads cnt / base of its inactive particles and nothing more. The other
+// walks keep a chain of dependent loads (the time bin, the owner, cnt / base,
+// the mark, the records, the window): the density walk sits at its register
+// limit and reloads spilled values inside its loop once the window is live
+// across load_i, and the gradient and limiter walks lose registers to it
+// (DESIGN 5).
+// fused: the loop folds in the pending init / reset of its fields (the stores
+// write their sums, not field + sum; swh_hydro.hip pending_take); an active
+// particle neither walked here nor queued for the overflow search gets the
+// initial values from its first lane. FZ: `fused` at compile time (0 / 1; -1:
+// the argument decides).
+template <int LOOP, typename T, int LPI, bool O32 = false, int FZ = -1>
 __device__ __forceinline__ void list_walk(const GridDev& g, SoA& a, const ListDev ld, int i0, int n,
                                           int max_active_bin, T a2H,
                                           const unsigned int* __restrict__ hmax_bits,
-                                          unsigned long long* counter, int* __restrict__ ncount) {
+                                          unsigned long long* counter, int* __restrict__ ncount,
+                                          int fused) {
   using S = LoopState<LOOP, T>;
+  const bool fz = FZ < 0 ? fused != 0 : FZ != 0;
+  constexpr bool kTwoTrip = SWH_WALK_TWO_TRIP && LOOP == LOOP_FORCE;
   constexpr int PPB = kWalkBlock / LPI;
   const int i = i0 + xcd_block_id() * PPB + (int)threadIdx.x / LPI;
   const int s = (int)threadIdx.x % LPI;
-  bool act = i < n && active_part(a, i, max_active_bin);
+  // (i >= 0: indexing by the unsigned value spares the sign-extended copy a
+  // register through the loop; the density walk has none to spare)
+  const unsigned int iu = (unsigned int)i;
+  bool live, act;
   int nl = 0, lb = 0;
-  if (act) {
-    nl = ld.cnt[i];
-    lb = ld.base[i];
-    if (nl > ld.K || lb < 0) act = false;  // overflow: the search walks it
-    if (ld.mark && ld.mark[i]) act = false;  // grown past the lists: searched
+  if constexpr (kTwoTrip) {
+    const bool in = i < n;
+    const int ic = in ? i : n - 1;  // (lanes past the end read the last particle's words)
+    const int tbi = a.tb[ic];
+    const int owner = a.perm[ic];
+    nl = ld.cnt[ic];
+    lb = ld.base[ic];
+    const unsigned int grown = ld.mark ? ld.mark[ic] : 0u;
+    live = in & (tbi <= max_active_bin) & (owner < a.n_owned);  // active_part
+    // overflow (the search walks it), not listed, or grown past the lists (searched)
+    act = live & (nl <= ld.K) & (lb >= 0) & (grown == 0u);
+  } else {
+    live = act = i < n && a.tb[iu] <= max_active_bin && a.perm[iu] < a.n_owned;
+    if (act) {
+      nl = ld.cnt[iu];
+      lb = ld.base[iu];
+      if (nl > ld.K || lb < 0) act = false;  // overflow: the search walks it
+      if (ld.mark && ld.mark[iu]) act = false;  // grown past the lists: searched
+    }
   }
+  // (a list longer than K was queued for the overflow search by the build).
+  // A guard: every entry that makes a particle active after the build
+  // (set_owned, the time step, the limiter apply, an upload) drops the lists,
+  // so a live particle without a list is not met in practice and no test
+  // reaches this store; it keeps "fused" from ever leaving a field unset.
+  const bool orphan = fz & live & !act & (nl <= ld.K) & (s == 0);
+  if constexpr (kTwoTrip)
+    if (!__any(act | orphan)) return;
   S st;
   st.n = 0;
-  double4 pi = make_double4(0., 0., 0., 0.);
+  PosRec pi = PosRec{};
+  int4 wv0 = make_int4(0, 0, 0, 0);
   if (act) {
-    st.load_i(a, i, a2H, hmax_bits);
-    pi = a.pos[i];
+    if constexpr (kTwoTrip) wv0 = walk_window0(ld, lb, s);
+    st.load_i(a, iu, a2H, hmax_bits, fz);
+    pi = a.pos[iu];
   }
   if (!act) nl = 0;
   const double rwrap = (double)__uint_as_float(*ld.rwrap_bits);
   if (__any(act && g.periodic && near_face(g, pi, rwrap)))
-    walk_entries<LPI, true, T, O32>(g, a, ld, pi, nl, lb, s, st);
+    walk_entries<LPI, true, T, O32, kTwoTrip>(g, a, ld, pi, nl, lb, s, st, wv0);
   else
-    walk_entries<LPI, false, T, O32>(g, a, ld, pi, nl, lb, s, st);
+    walk_entries<LPI, false, T, O32, kTwoTrip>(g, a, ld, pi, nl, lb, s, st, wv0);
   reduce_lanes<LPI, T>(st);
   if (act && s == 0) {
-    st.store(a, i);
-    if (ncount) ncount[i] = st.n;
+    st.store(a, iu, fz);
+    if (ncount) ncount[iu] = st.n;
   }
+  if (orphan) S::store_init(a, iu);
   if (counter) {
     unsigned long long v = (unsigned long long)((act && s == 0) ? st.n : 0);
     v = wave_sum_ull(v);

@@ -5,9 +5,30 @@
 
 namespace swh {
 
+// A particle's position record: 32 bytes, read by every loop as two 16-byte
+// words. h is SWIFT's float; the four bytes beside it carry the particle's
+// time bin, so a loop that gathers the position has the bin with it (the force
+// and limiter walks need both). meta: bits 0-7 the time bin (int8), bits 8-31
+// zero and free. SoA::tb stays the array the streaming kernels read; every
+// writer of a bin (unpack_kernel, the rebuild's permute, the time step, the
+// limiter's apply) writes both, and every writer of a position keeps meta.
+struct alignas(32) PosRec {
+  double x, y, z;
+  float h;
+  int meta;
+};
+static_assert(sizeof(PosRec) == 32, "two 16-byte words per particle");
+__host__ __device__ __forceinline__ PosRec make_pos(double x, double y, double z, float h,
+                                                    int bin) {
+  return PosRec{x, y, z, h, bin & 0xff};
+}
+__host__ __device__ __forceinline__ float h_of(const PosRec& p) { return p.h; }
+__host__ __device__ __forceinline__ int bin_of(const PosRec& p) { return (int)(int8_t)p.meta; }
+__host__ __device__ __forceinline__ void set_bin(PosRec& p, int bin) { p.meta = bin & 0xff; }
+
 // Sorted SoA arrays of a swh_space (device pointers, passed by value).
 struct SoA {
-  double4* pos;   // x, y, z, h
+  PosRec* pos;    // x, y, z, h, time bin
   float4* vm;     // vx, vy, vz, mass
   float4* th;     // u, rho, pressure, soundspeed
   float4* fc;     // f (grad-h), balsara, alpha_visc, alpha_diff

@@ -33,7 +33,8 @@ __global__ void unpack_kernel(Layout L, const char* __restrict__ aos, int64_t n,
   const char* r = aos + i * L.stride;
   hasg[i] = (L.gpart >= 0 && *reinterpret_cast<void* const*>(r + L.gpart) != nullptr) ? 1 : 0;
   const double* x = reinterpret_cast<const double*>(r + L.x);
-  a.pos[i] = make_double4(x[0], x[1], x[2], (double)aos_f(r, L.h));
+  a.pos[i] = make_pos(x[0], x[1], x[2], aos_f(r, L.h),
+                      *reinterpret_cast<const int8_t*>(r + L.time_bin));
   a.vm[i] = make_float4(aos_f(r, L.v), aos_f(r, L.v + 4), aos_f(r, L.v + 8), aos_f(r, L.mass));
   a.th[i] = make_float4(aos_f(r, L.u), aos_f(r, L.rho), aos_f(r, L.pressure),
                         aos_f(r, L.soundspeed));
@@ -61,12 +62,12 @@ __global__ void pack_kernel(Layout L, char* __restrict__ aos, int64_t n, SoA a, 
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;
   char* r = aos + (int64_t)a.perm[s] * L.stride;
-  const double4 p = a.pos[s];
+  const PosRec p = a.pos[s];
   const float4 th = a.th[s];
   if (fields & SWH_FIELDS_DENSITY) {
     const float4 d = a.dens[s];
     const float4 rt = a.rot[s];
-    put_f(r, L.h, (float)p.w);
+    put_f(r, L.h, h_of(p));
     put_f(r, L.rho, th.y);
     put_f(r, L.rho_dh, d.x);
     put_f(r, L.wcount, d.y);
@@ -82,7 +83,7 @@ __global__ void pack_kernel(Layout L, char* __restrict__ aos, int64_t n, SoA a, 
     const float4 rt = a.rot[s];
     const float4 g = a.grad[s];
     const float4 fc = a.fc[s];
-    put_f(r, L.h, (float)p.w);
+    put_f(r, L.h, h_of(p));
     put_f(r, L.rho, th.y);
     put_f(r, L.div_v, d.w);
     put_f(r, L.laplace_u, rt.w);
@@ -115,7 +116,7 @@ __global__ void pack_kernel(Layout L, char* __restrict__ aos, int64_t n, SoA a, 
     put_f(r, L.v, vm.x);
     put_f(r, L.v + 4, vm.y);
     put_f(r, L.v + 8, vm.z);
-    put_f(r, L.h, (float)p.w);
+    put_f(r, L.h, h_of(p));
     put_f(r, L.u, th.x);
     put_f(r, L.rho, th.y);
     put_f(r, L.pressure, th.z);
@@ -126,7 +127,7 @@ __global__ void pack_kernel(Layout L, char* __restrict__ aos, int64_t n, SoA a, 
 }
 
 // Per-block partial bounding box + max h over non-inhibited particles.
-__global__ void bbox_kernel(const double4* __restrict__ pos, const int8_t* __restrict__ tb,
+__global__ void bbox_kernel(const PosRec* __restrict__ pos, const int8_t* __restrict__ tb,
                             int64_t n, double* out) {
   // per block: min x,y,z; max x,y,z; max h; sum of log h (the grid's typical h)
   __shared__ double red[8][256];
@@ -134,11 +135,11 @@ __global__ void bbox_kernel(const double4* __restrict__ pos, const int8_t* __res
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     if (tb[i] == kTimeBinInhibited) continue;
-    const double4 p = pos[i];
+    const PosRec p = pos[i];
     v[0] = fmin(v[0], p.x); v[1] = fmin(v[1], p.y); v[2] = fmin(v[2], p.z);
     v[3] = fmax(v[3], p.x); v[4] = fmax(v[4], p.y); v[5] = fmax(v[5], p.z);
-    v[6] = fmax(v[6], p.w);
-    v[7] += p.w > 0. ? log(p.w) : 0.;
+    v[6] = fmax(v[6], (double)h_of(p));
+    v[7] += (double)h_of(p) > 0. ? log((double)h_of(p)) : 0.;
   }
   for (int k = 0; k < 8; k++) red[k][threadIdx.x] = v[k];
   __syncthreads();
@@ -164,7 +165,7 @@ __device__ __forceinline__ uint32_t spread3(uint32_t v);
 // the particle's Morton position inside its cell: a cell stays one
 // contiguous range, and inside it particles close in space are close in
 // memory, so the neighbours a list entry names sit in few cache lines.
-__global__ void key_kernel(GridDev g, const int* __restrict__ rank, double4* __restrict__ pos,
+__global__ void key_kernel(GridDev g, const int* __restrict__ rank, PosRec* __restrict__ pos,
                            const int8_t* __restrict__ tb, int64_t n, int ncell, int sb,
                            uint32_t* __restrict__ keys, int* __restrict__ idx) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -174,7 +175,7 @@ __global__ void key_kernel(GridDev g, const int* __restrict__ rank, double4* __r
     keys[i] = (uint32_t)ncell << (3 * sb);
     return;
   }
-  double4 p = pos[i];
+  PosRec p = pos[i];
   if (g.periodic) {  // box-wrap as space_rebuild does
     p.x -= floor(p.x / g.dim[0]) * g.dim[0];
     p.y -= floor(p.y / g.dim[1]) * g.dim[1];
@@ -390,7 +391,7 @@ __global__ void halo_pack_kernel(SoA a, const int* __restrict__ idx, int n,
   if (t >= n) return;
   const int s = a.iperm[idx[t]];
   const float4 th = a.th[s];
-  out[2 * t] = make_float4((float)a.pos[s].w, th.y, th.z, th.w);
+  out[2 * t] = make_float4(h_of(a.pos[s]), th.y, th.z, th.w);
   out[2 * t + 1] = a.fc[s];
 }
 
@@ -402,7 +403,7 @@ __global__ void halo_unpack_kernel(SoA a, const int* __restrict__ idx, int n,
   const int s = a.iperm[idx[t]];
   const float4 r0 = in[2 * t], r1 = in[2 * t + 1];
   if (mask & SWH_HALO_H) {
-    a.pos[s].w = (double)r0.x;
+    a.pos[s].h = r0.x;  // (the time bin beside it stays)
     atomic_max_bits_if(hmax_bits, __float_as_uint(r0.x));
   }
   float4 th = a.th[s];
@@ -506,7 +507,7 @@ __global__ __launch_bounds__(256) void drift_kernel(SoA a, const float4* __restr
     if (a.tb[s] == kTimeBinInhibited) continue;
     const int c = (int)s;  // vfull / agrav / hasg in sorted order (xsort_kernel)
     const float4 vf = vfull[c];
-    double4 p = a.pos[s];
+    PosRec p = a.pos[s];
     p.x += (double)vf.x * D.dt_drift;
     p.y += (double)vf.y * D.dt_drift;
     p.z += (double)vf.z * D.dt_drift;
@@ -526,7 +527,7 @@ __global__ __launch_bounds__(256) void drift_kernel(SoA a, const float4* __restr
     // hydro_predict_extra
     float4 th = a.th[s];  // u, rho, P, c
     th.x += ac.w * (float)D.dt_therm;
-    float h = (float)p.w;
+    float h = h_of(p);
     const float h_inv = 1.f / h;
     const float w1 = a.hdt[s] * h_inv * (float)D.dt_drift;
     h *= fabsf(w1) < 0.2f ? approx_expf(w1) : expf(w1);
@@ -543,7 +544,7 @@ __global__ __launch_bounds__(256) void drift_kernel(SoA a, const float4* __restr
     float4 gr = a.grad[s];
     gr.x = fmaxf(gr.x, 2.f * soundspeed);
     a.grad[s] = gr;
-    p.w = (double)h;
+    p.h = h;
     a.pos[s] = p;
     // offsets since the last rebuild (xp->x_diff)
     float4 xd = xdiff[s];
@@ -568,13 +569,13 @@ __global__ void cell_start_kernel(const uint32_t* __restrict__ keys, int64_t n, 
   for (int64_t c = prev + 1; c <= cur; c++) start[c] = (int)i;
 }
 
-__global__ __launch_bounds__(256) void hmax_kernel(const double4* __restrict__ pos, const int8_t* __restrict__ tb,
+__global__ __launch_bounds__(256) void hmax_kernel(const PosRec* __restrict__ pos, const int8_t* __restrict__ tb,
                             int64_t n, unsigned int* out_bits) {
   __shared__ float sm[4];
   float m = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
-    if (tb[i] != kTimeBinInhibited) m = fmaxf(m, (float)pos[i].w);
+    if (tb[i] != kTimeBinInhibited) m = fmaxf(m, h_of(pos[i]));
   block_max_bits(out_bits, m, sm);
 }
 
@@ -590,7 +591,7 @@ namespace swh {
 
 SoA soa_of(swh_space* s) {
   SoA a;
-  a.pos = s->pos.as<double4>();
+  a.pos = s->pos.as<PosRec>();
   a.vm = s->vm.as<float4>();
   a.th = s->th.as<float4>();
   a.fc = s->fc.as<float4>();
@@ -608,7 +609,7 @@ SoA soa_of(swh_space* s) {
 }
 
 static size_t soa_bytes_per_part() {
-  return sizeof(double4) + 7 * sizeof(float4) + sizeof(float) + 2 * sizeof(int8_t) +
+  return sizeof(PosRec) + 7 * sizeof(float4) + sizeof(float) + 2 * sizeof(int8_t) +
          sizeof(int);
 }
 
@@ -621,7 +622,7 @@ static SoA soa_carve(char* base, int64_t n) {
     off += (bytes + 255) & ~size_t(255);
     return p;
   };
-  a.pos = reinterpret_cast<double4*>(take(n * sizeof(double4)));
+  a.pos = reinterpret_cast<PosRec*>(take(n * sizeof(PosRec)));
   a.vm = reinterpret_cast<float4*>(take(n * sizeof(float4)));
   a.th = reinterpret_cast<float4*>(take(n * sizeof(float4)));
   a.fc = reinterpret_cast<float4*>(take(n * sizeof(float4)));
@@ -640,7 +641,7 @@ static SoA soa_carve(char* base, int64_t n) {
 
 static swh_status copy_soa(const SoA& src, swh_space* s, hipStream_t st) {
   const int64_t n = s->n;
-  SWH_HIP(hipMemcpyAsync(s->pos.ptr, src.pos, n * sizeof(double4), hipMemcpyDeviceToDevice, st));
+  SWH_HIP(hipMemcpyAsync(s->pos.ptr, src.pos, n * sizeof(PosRec), hipMemcpyDeviceToDevice, st));
   SWH_HIP(hipMemcpyAsync(s->vm.ptr, src.vm, n * sizeof(float4), hipMemcpyDeviceToDevice, st));
   SWH_HIP(hipMemcpyAsync(s->th.ptr, src.th, n * sizeof(float4), hipMemcpyDeviceToDevice, st));
   SWH_HIP(hipMemcpyAsync(s->fc.ptr, src.fc, n * sizeof(float4), hipMemcpyDeviceToDevice, st));
@@ -656,7 +657,7 @@ static swh_status copy_soa(const SoA& src, swh_space* s, hipStream_t st) {
 }
 
 static swh_status reserve_soa(swh_space* s, int64_t n) {
-  SWH_TRY(s->pos.reserve(n * sizeof(double4)));
+  SWH_TRY(s->pos.reserve(n * sizeof(PosRec)));
   SWH_TRY(s->vm.reserve(n * sizeof(float4)));
   SWH_TRY(s->th.reserve(n * sizeof(float4)));
   SWH_TRY(s->fc.reserve(n * sizeof(float4)));
@@ -680,7 +681,7 @@ swh_status space_hmax_to_device(swh_space* s) {
   }
   unsigned int* hb = s->counters.as<unsigned int>() + 2;  // slot 2: hmax bits
   SWH_HIP(hipMemsetAsync(hb, 0, sizeof(unsigned int), s->stream));
-  hipLaunchKernelGGL(hmax_kernel, dim3(1024), dim3(256), 0, s->stream, s->pos.as<double4>(),
+  hipLaunchKernelGGL(hmax_kernel, dim3(1024), dim3(256), 0, s->stream, s->pos.as<PosRec>(),
                      s->tb.as<int8_t>(), s->n, hb);
   SWH_HIP(hipGetLastError());
   return SWH_OK;
@@ -735,6 +736,7 @@ swh_status swh_space_create(swh_context* ctx, swh_space** out) {
 }
 
 swh_status swh_space_destroy(swh_space* s) {
+  (void)swh::space_apply_pending(s);
   if (!s) return SWH_OK;
   (void)hipSetDevice(s->ctx->device);
   (void)hipStreamSynchronize(s->stream);
@@ -760,6 +762,7 @@ swh_status swh_space_destroy(swh_space* s) {
 }
 
 swh_status swh_space_set_stream(swh_space* s, void* stream) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s) return SWH_ERR_ARG;
   if (stream) {
     if (s->own_stream && s->stream) {
@@ -773,6 +776,7 @@ swh_status swh_space_set_stream(swh_space* s, void* stream) {
 }
 
 swh_status swh_space_set_tuning(swh_space* s, const swh_tuning* t) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || !t || t->cell_factor < 1 || t->cell_factor > 4 ||
       (t->loop_variant != 0 && t->loop_variant != 7) ||
       (t->group_size != 0 && t->group_size != 16) || t->cell_scale < 0.f || t->cell_scale > 4.f ||
@@ -817,6 +821,7 @@ swh_status swh_space_get_info(const swh_space* s, swh_space_info* info) {
 
 swh_status swh_space_upload_xparts(swh_space* s, const void* xparts, int64_t count,
                                    const swh_xpart_layout* XL, int on_device) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || !XL || (count > 0 && !xparts) || count != s->n || XL->stride <= 0 ||
       XL->off_v_full < 0 || XL->off_v_full + 12 > XL->stride ||
       (XL->off_a_grav >= 0 && XL->off_a_grav + 12 > XL->stride) ||
@@ -863,6 +868,7 @@ swh_status swh_space_upload_xparts(swh_space* s, const void* xparts, int64_t cou
 }
 
 swh_status swh_space_drift(swh_space* s, const swh_drift_params* D, const swh_hydro_params* P) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || !D || !P) return SWH_ERR_ARG;
   if (!s->built) {
     set_error("swh_space_rebuild must precede the drift");
@@ -905,12 +911,14 @@ swh_status swh_space_drift(swh_space* s, const swh_drift_params* D, const swh_hy
 }
 
 swh_status swh_space_sync(swh_space* s) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s) return SWH_ERR_ARG;
   SWH_HIP(hipStreamSynchronize(s->stream));
   return SWH_OK;
 }
 
 swh_status swh_space_query(swh_space* s) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s) return SWH_ERR_ARG;
   const hipError_t e = hipStreamQuery(s->stream);
   if (e == hipErrorNotReady) return SWH_BUSY;
@@ -920,6 +928,7 @@ swh_status swh_space_query(swh_space* s) {
 
 swh_status swh_space_upload_parts(swh_space* s, const void* parts, int64_t count,
                                   const swh_part_layout* PL, int on_device) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || (count > 0 && !parts) || count < 0 || count > INT32_MAX / 2 || !PL)
     return SWH_ERR_ARG;
   Layout L;
@@ -957,6 +966,7 @@ swh_status swh_space_upload_parts(swh_space* s, const void* parts, int64_t count
 
 swh_status swh_space_download_parts(swh_space* s, void* parts, const swh_part_layout* PL,
                                     int fields, int on_device) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || (s->n > 0 && !parts) || !PL) return SWH_ERR_ARG;
   Layout L;
   SWH_TRY(make_layout(PL, &L));
@@ -979,6 +989,7 @@ swh_status swh_space_download_parts(swh_space* s, void* parts, const swh_part_la
 }
 
 swh_status swh_space_set_owned(swh_space* s, int64_t n_owned) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || n_owned < 0 || n_owned > s->n) return SWH_ERR_ARG;
   if (n_owned < s->n) couple_unlink(s);  // the link covers one device's particles only
   s->n_owned = n_owned;
@@ -996,6 +1007,7 @@ static swh_status halo_check(swh_space* s, const int32_t* idx, int32_t n, const 
 }
 
 swh_status swh_space_pack_halo(swh_space* s, const int32_t* idx, int32_t n, float* out) {
+  SWH_TRY(swh::space_apply_pending(s));
   SWH_TRY(halo_check(s, idx, n, out));
   if (n == 0) return SWH_OK;
   SWH_HIP(hipSetDevice(s->ctx->device));
@@ -1007,6 +1019,7 @@ swh_status swh_space_pack_halo(swh_space* s, const int32_t* idx, int32_t n, floa
 
 swh_status swh_space_unpack_halo(swh_space* s, const int32_t* idx, int32_t n, const float* in,
                                  int fields) {
+  SWH_TRY(swh::space_apply_pending(s));
   SWH_TRY(halo_check(s, idx, n, in));
   if (fields & ~SWH_HALO_ALL) return SWH_ERR_ARG;
   if (n == 0) return SWH_OK;
@@ -1021,6 +1034,7 @@ swh_status swh_space_unpack_halo(swh_space* s, const int32_t* idx, int32_t n, co
 }
 
 swh_status swh_space_rebuild(swh_space* s, const swh_hydro_params* P, double min_cell_width) {
+  SWH_TRY(swh::space_apply_pending(s));
   if (!s || !P) return SWH_ERR_ARG;
   const int64_t n = s->n;
   if (n == 0) {
@@ -1040,7 +1054,7 @@ swh_status swh_space_rebuild(swh_space* s, const swh_hydro_params* P, double min
   const int nb = 512;
   SWH_TRY(s->scan_tmp.reserve(nb * 8 * sizeof(double)));
   SWH_TRY(s->hstage.reserve(nb * 8 * sizeof(double)));
-  hipLaunchKernelGGL(bbox_kernel, dim3(nb), dim3(256), 0, st, s->pos.as<double4>(),
+  hipLaunchKernelGGL(bbox_kernel, dim3(nb), dim3(256), 0, st, s->pos.as<PosRec>(),
                      s->tb.as<int8_t>(), n, s->scan_tmp.as<double>());
   SWH_HIP(hipGetLastError());
   SWH_HIP(hipMemcpyAsync(s->hstage.ptr, s->scan_tmp.ptr, nb * 8 * sizeof(double),
@@ -1152,7 +1166,7 @@ swh_status swh_space_rebuild(swh_space* s, const swh_hydro_params* P, double min
   int sub_bits = std::min(3, (32 - end_bit) / 3);
   if (const char* e = std::getenv("SWH_SUBCELL_BITS")) sub_bits = std::max(0, std::min(sub_bits, std::atoi(e)));
   hipLaunchKernelGGL(key_kernel, dim3(grid), dim3(block), 0, st, gd,
-                     s->cell_rank.as<const int>(), s->pos.as<double4>(),
+                     s->cell_rank.as<const int>(), s->pos.as<PosRec>(),
                      s->tb.as<const int8_t>(), n, g.ncell, sub_bits, s->keys.as<uint32_t>(),
                      s->idx.as<int>());
   SWH_HIP(hipGetLastError());
