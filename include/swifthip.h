@@ -44,6 +44,8 @@
 extern "C" {
 #endif
 
+/* v15 also gained, without a new number (purely additive: no struct or
+ * signature moved), the statistics entries at the end of this header. */
 #define SWH_ABI_VERSION 15
 
 #if defined(__GNUC__)
@@ -1055,6 +1057,78 @@ SWH_API swh_status swh_space_end_step_limited_linked(
  * stream the stage runs on; waits for them): ms[0..3) = pull, push, the last
  * linked kick1 / kick2 / timestep / end_step. -1 for a stage not yet run. */
 SWH_API swh_status swh_space_link_times(swh_space *s, float *ms);
+
+/* ------------------------------------------------------------------ */
+/* Conserved-quantity statistics and synchronised velocities (added to */
+/* ABI v15; purely additive). SWIFT's stats_collect                    */
+/* (src/statistics.c:131-261, 545-627) over a space and a gspace, and  */
+/* the "snapshot" velocity of every particle: v_full sits at the       */
+/* middle of the particle's step and is extrapolated to ti_current     */
+/* with the stored accelerations (convert_part_vel,                    */
+/* src/hydro/SPHENIX/hydro_io.h:100-150; convert_gpart_vel,            */
+/* src/gravity/MultiSoftening/gravity_io.h:45-78). Nothing here drops  */
+/* pair lists, marks a tree stale or writes a byte of a particle.      */
+/* ------------------------------------------------------------------ */
+typedef struct swh_stats_params {
+  int64_t ti_current;
+  double time_base;
+  int32_t extrapolate; /* 0: v_full as stored (between the first forces and the first kick1) */
+  int32_t periodic;    /* positions through box_wrap(x, 0, dim) */
+  double dim[3];
+  float a_inv, a_factor_internal_energy; /* 1, 1 without cosmology */
+  double dt_kick_mesh_grav; /* src/engine_io.c:314-320, used as a float; 0 without a mesh */
+  /* Per time bin (SWH_NUM_TIME_BINS + 1 entries), nullable together: the
+   * integral of the hydro / gravity kick factor from the middle of the bin's
+   * step to ti_current. NULL: (ti_current - (ti_beg + ti_end) / 2) * time_base. */
+  const double *dt_sync_hydro, *dt_sync_grav;
+} swh_stats_params;
+
+/* Partial sums, not finalised: com = sum m x. */
+typedef struct swh_statistics {
+  double E_kin, E_int, E_pot_self, entropy, gas_mass, dm_mass;
+  double mom[3], ang_mom[3], com[3];
+  int64_t n_counted; /* gas particles (space) or dark-matter gparts (gspace) summed */
+} swh_statistics;
+
+/* The sums over the space's own (swh_space_set_owned) particles that are
+ * neither inhibited nor not-yet-created: one launch and a one-wave reduction
+ * on the space's stream, the result copied to pinned host memory behind them;
+ * no host wait. The gravity term of the velocities is what the space's kicks
+ * read: xp->a_grav and the gpart flag of an unlinked space (mesh term 0), the
+ * pulled a_grav / a_grav_mesh of a linked one (SWH_ERR_STATE without a
+ * swh_space_pull_gravity since the last rebuild). E_pot_self of the gas is
+ * collected on the gspace. No floating-point atomics: the same state gives the
+ * same bits on every call (a rebuild that changes the sort order may change
+ * the last bits). SWH_ERR_STATE before swh_space_upload_xparts / _rebuild. */
+SWH_API swh_status swh_space_statistics(swh_space *s, const swh_stats_params *P);
+/* Waits for the last swh_space_statistics; SWH_ERR_STATE if there was none.
+ * An empty space gives zeros. */
+SWH_API swh_status swh_space_statistics_result(swh_space *s, swh_statistics *out);
+/* v: n x 3 floats in caller order (host, or device memory with on_device),
+ * the synchronised velocity of every particle; 0 for inhibited and foreign
+ * ones. With on_device the kernel writes v itself, else a scratch that is then
+ * copied to the host. Waits for the stream either way. */
+SWH_API swh_status swh_space_sync_velocities(swh_space *s, const swh_stats_params *P, float *v,
+                                             int on_device);
+/* The same over the stored records of a gspace (after swh_gspace_upload and
+ * swh_gspace_set_step_layout): dark-matter and background gparts (types 1, 2)
+ * give the dm sums, a live gas gpart (type 0) E_pot_self = 0.5 mass potential
+ * a_inv of the gas (the reference multiplies by the part's mass,
+ * statistics.c:238-239; the link keeps the two equal), other types nothing.
+ * Velocities in record order, as swh_gspace_download returns the records. */
+SWH_API swh_status swh_gspace_statistics(swh_gspace *g, const swh_stats_params *P);
+SWH_API swh_status swh_gspace_statistics_result(swh_gspace *g, swh_statistics *out);
+SWH_API swh_status swh_gspace_sync_velocities(swh_gspace *g, const swh_stats_params *P, float *v,
+                                              int on_device);
+/* Device time of the last statistics launches (the blocks' kernel and the
+ * one-wave reduction) and of the last velocity launch (ms, HIP events on the
+ * object's stream; waits for them): ms[0..2). -1 for a stage not yet run. */
+SWH_API swh_status swh_space_statistics_times(swh_space *s, float *ms);
+SWH_API swh_status swh_gspace_statistics_times(swh_gspace *g, float *ms);
+/* Host only. a += b (stats_add, statistics.c:69); total mass = gas + dm and
+ * com /= total mass when it is positive (stats_finalize, statistics.c:678). */
+SWH_API void swh_statistics_add(swh_statistics *a, const swh_statistics *b);
+SWH_API void swh_statistics_finalize(swh_statistics *a);
 
 #ifdef __cplusplus
 }

@@ -405,6 +405,66 @@ class PushParams(C.Structure):
         super().__init__(int(what), int(periodic), (C.c_double * 3)(*dim))
 
 
+TIME_BIN_NOT_CREATED = NUM_TIME_BINS + 1  # src/timeline.h time_bin_not_created
+
+
+class StatsParams(C.Structure):
+    """swh_stats_params: the statistics and the synchronised velocities at
+    ti_current (non-cosmological unless set_tables and the two factors)."""
+
+    _fields_ = [("ti_current", C.c_int64), ("time_base", C.c_double),
+                ("extrapolate", C.c_int32), ("periodic", C.c_int32), ("dim", C.c_double * 3),
+                ("a_inv", C.c_float), ("a_factor_internal_energy", C.c_float),
+                ("dt_kick_mesh_grav", C.c_double),
+                ("dt_sync_hydro", C.POINTER(C.c_double)),
+                ("dt_sync_grav", C.POINTER(C.c_double))]
+
+    def __init__(self, ti_current=0, time_base=0.0, extrapolate=1, periodic=0,
+                 dim=(1.0, 1.0, 1.0), a_inv=1.0, a_factor_internal_energy=1.0,
+                 dt_kick_mesh_grav=0.0):
+        super().__init__(int(ti_current), float(time_base), int(extrapolate), int(periodic),
+                         (C.c_double * 3)(*dim), a_inv, a_factor_internal_energy,
+                         float(dt_kick_mesh_grav))
+
+    def set_tables(self, hydro=None, grav=None) -> None:
+        """Per-time-bin time from mid-step to ti_current (cosmo.sync_tables),
+        both or neither. The arrays are kept alive by this object."""
+        if (hydro is None) != (grav is None):
+            raise ValueError("the hydro and the gravity table are given together")
+        self._keep = []
+        for name, tab in (("dt_sync_hydro", hydro), ("dt_sync_grav", grav)):
+            arr, ptr = _bin_table(tab)
+            self._keep.append(arr)
+            setattr(self, name, ptr)
+
+
+STATISTICS_SCALARS = ("E_kin", "E_int", "E_pot_self", "entropy", "gas_mass", "dm_mass")
+STATISTICS_VECTORS = ("mom", "ang_mom", "com")
+
+
+class Statistics(C.Structure):
+    """swh_statistics: partial sums (com = sum m x until finalised)."""
+
+    _fields_ = ([(n, C.c_double) for n in STATISTICS_SCALARS] +
+                [(n, C.c_double * 3) for n in STATISTICS_VECTORS] + [("n_counted", C.c_int64)])
+
+    def as_dict(self) -> dict:
+        d = {n: float(getattr(self, n)) for n in STATISTICS_SCALARS}
+        d.update({n: np.array(getattr(self, n), dtype=np.float64) for n in STATISTICS_VECTORS})
+        d["n_counted"] = int(self.n_counted)
+        return d
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "Statistics":
+        s = cls()
+        for n in STATISTICS_SCALARS:
+            setattr(s, n, float(d[n]))
+        for n in STATISTICS_VECTORS:
+            setattr(s, n, (C.c_double * 3)(*[float(v) for v in d[n]]))
+        s.n_counted = int(d["n_counted"])
+        return s
+
+
 class GCell(C.Structure):
     """swh_gcell: a tree cell's gpart range, progeny and geometry."""
 

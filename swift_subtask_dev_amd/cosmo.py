@@ -190,6 +190,30 @@ def limiter_tables(cosmo: Cosmology, ti_current: int) -> tuple:
     return first, since
 
 
+def sync_tables(cosmo: Cosmology, ti_current: int) -> dict:
+    """swh_stats_params' per-bin tables at ti_current with cosmology: for every
+    bin the integral of the hydro / gravity kick factor from the middle of the
+    step that holds ti_current (ti_current itself counts as the end of the
+    step before it, timeline.h:107-134) to ti_current -- negative in the first
+    half of a step. convert_part_vel (hydro_io.h:115-121) subtracts two
+    interpolated integrals from ti_beg, each rounded to float; this is the
+    integral itself by the Gauss-Legendre rule of kick_tables, rounded once
+    where it is used."""
+    out = {k: np.zeros(NUM_TIME_BINS + 1) for k in ("hydro", "grav")}
+    powers = {"grav": 1.0, "hydro": 3.0 * (HYDRO_GAMMA - 1.0)}
+    for b in range(1, NUM_TIME_BINS + 1):
+        step = get_integer_timestep(b)
+        beg = get_integer_time_begin(ti_current, b) if ti_current > 0 else 0
+        end = ti_current if ti_current % step == 0 else ti_current - ti_current % step + step
+        mid = (beg + end) // 2
+        if end > MAX_NR_TIMESTEPS or mid == ti_current:
+            continue  # no such step on the time line / nothing to extrapolate
+        for k, p in powers.items():
+            out[k][b] = (_kick_integral(cosmo, mid, ti_current, p) if mid < ti_current
+                         else -_kick_integral(cosmo, ti_current, mid, p))
+    return out
+
+
 def cosmological_params(cosmo: Cosmology, ti_current: int, dim=(1.0, 1.0, 1.0),
                         periodic=True, **kw) -> abi.HydroParams:
     """swh_hydro_params of a cosmological step: a, H, a^-2 and the gamma = 5/3

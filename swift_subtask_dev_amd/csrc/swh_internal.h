@@ -158,6 +158,30 @@ struct StageTimer {
   }
 };
 
+// The statistics of a space or a gspace (swh_stats.hip), host side: the
+// blocks' partial sums, the reduced record, its pinned copy and the event
+// behind the last copy; the scratch of the synchronised velocities; HIP events
+// around the last statistics and the last velocity launch.
+struct StatsState {
+  DevBuf partials, out, vel;
+  HostBuf host;
+  hipEvent_t event = nullptr;
+  bool pending = false;  // a copy is queued and not yet waited for
+  bool has = false;      // host holds the result of some call
+  StageTimer<2> timer;   // statistics (both kernels), sync velocities
+  void release() {
+    partials.release();
+    out.release();
+    vel.release();
+    host.release();
+    if (event) (void)hipEventDestroy(event);
+    event = nullptr;
+    timer.release();
+    pending = has = false;
+  }
+  ~StatsState() { release(); }  // with its space (swh_space_destroy's delete)
+};
+
 // Device copy of the AoS layout (offsets), passed by value to kernels.
 struct Layout {
   int stride;
@@ -290,6 +314,7 @@ struct swh_space {
   hipEvent_t link_event = nullptr;  // recorded on this space's stream for the gspace's
   // the last pull, push and linked kick / timestep launch (swh_space_link_times)
   swh::StageTimer<3> link_timer;
+  swh::StatsState stats;  // swh_space_statistics / _sync_velocities (swh_stats.hip)
   // grid
   swh::DevBuf cell_start;  // int32[ncell+1], indexed by Morton rank
   swh::DevBuf cell_rank;   // int32[ncell]: linear cell -> Morton rank
@@ -424,6 +449,7 @@ struct swh_gspace {
   // gas <-> gpart link (swh_couple.hip)
   swh_space* link = nullptr;
   hipEvent_t link_event = nullptr;  // recorded on this gspace's stream for the space's
+  swh::StatsState stats;  // swh_gspace_statistics / _sync_velocities (swh_stats.hip)
 };
 
 namespace swh {

@@ -130,6 +130,12 @@ __device__ __forceinline__ double wave_max_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
   return v;
 }
+// Sum over the 64 lanes in a fixed order (a butterfly: lane i adds lane i ^ o,
+// and a + b == b + a, so every lane ends with the same bits on every run).
+__device__ __forceinline__ double wave_sum_d(double v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 // Wave-uniform max / min of a double that is equal within each quad of
 // lanes (the list build's four lanes per i): two DPP mirrors combine the
 // quads of each 16-lane row, four readlanes the rows -- no LDS round trip

@@ -20,6 +20,18 @@ which bounds the next drift's displacement. Particles are re-binned
 `max_rel_dx` of the smallest cell width -- SWIFT's space_maxreldx (space.h:66,
 default 0.1).
 
+statistics=True on init_step / drift_to_next / step of any of the three
+drivers collects SWIFT's stats_collect (energies, momentum, angular momentum,
+centre of mass) on the device and appends (ti_current, dict) to
+self.statistics. The collection point is fixed by what the fields mean: after
+the drift (positions, u and rho at ti_current, every v_full at the middle of
+the step that holds ti_current, the accelerations those of the particle's last
+kick, so the velocities are extrapolated to ti_current as a snapshot's are),
+before a rebuild of the space (it voids a linked space's pulled accelerations)
+and before the forces (they zero the active particles' accelerations). In
+init_step it sits between the first forces and the first kick1, with v_full as
+stored. With statistics=False nothing changes.
+
 Non-cosmological by default (time_base = the physical time of one tick of the
 integer time line). With a cosmo.Cosmology the time line runs in log a: the
 drift and kick factors are the integrals of cosmo.kick_tables, the engine
@@ -29,7 +41,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import abi, cosmo as cosmo_mod, ics
+from . import abi, cosmo as cosmo_mod, ics, lib
 
 MAX_NR_TIMESTEPS = 1 << (abi.NUM_TIME_BINS + 1)
 
@@ -65,6 +77,7 @@ class Integrator:
         self.limiter = bool(limiter)
         # running counts of the limited steps (limiter=True)
         self.limited = {"n_woken_active": 0, "n_woken_inactive": 0, "min_new_bin": None}
+        self.statistics = []  # (ti_current, finalised statistics) of the collected steps
         self.P.time_base = self.time_base
         self.T.time_base_inv = 1.0 / self.time_base
 
@@ -118,8 +131,25 @@ class Integrator:
                                ki(cm, ti_old, ti_new, 1.0), ki(cm, ti_old, ti_new, 2.0),
                                self.min_u)
 
+    def _stats_params(self, extrapolate: int = 1) -> abi.StatsParams:
+        dim = tuple(self.P.dim)
+        cm = self.cosmology
+        if cm is None:
+            return abi.StatsParams(self.ti_current, self.time_base, extrapolate,
+                                   self.P.periodic, dim)
+        a = cm.scale_factor(self.ti_current)
+        S = abi.StatsParams(self.ti_current, self.time_base, extrapolate, self.P.periodic, dim,
+                            1.0 / a, a ** (-3.0 * (cosmo_mod.HYDRO_GAMMA - 1.0)))
+        S.set_tables(**cosmo_mod.sync_tables(cm, self.ti_current))
+        return S
+
+    def collect_statistics(self, extrapolate: int = 1) -> dict:
+        st = lib.finalize_statistics(self.sp.statistics(self._stats_params(extrapolate)))
+        self.statistics.append((self.ti_current, st))
+        return st
+
     # -- the two entry points -----------------------------------------------
-    def init_step(self, parts: np.ndarray, xparts: np.ndarray) -> dict:
+    def init_step(self, parts: np.ndarray, xparts: np.ndarray, statistics: bool = False) -> dict:
         """Upload the particles (the only upload of the run), compute their
         first forces, time steps and half-kick. Particles start in time bin 0
         (hydro_first_init_part), as in engine_init_particles."""
@@ -133,12 +163,15 @@ class Integrator:
         self.sp.rebuild(self.P)
         self.sp.upload_xparts(xparts)
         self.chain = self.sp.hydro_step(self.P)
+        self.statistics = []
+        if statistics:
+            self.collect_statistics(extrapolate=0)
         self.sp.timestep(self.T, self.P)
         self.sp.kick1(self._kick_params(1), self.P)
         self.result = self.sp.step_result()
         return self.result
 
-    def drift_to_next(self) -> abi.DriftParams:
+    def drift_to_next(self, statistics: bool = False) -> abi.DriftParams:
         """First part of step(): choose the next ti_current and drift there."""
         ti_old = self.ti_current
         self.ti_current = int(self.result["ti_end_min"])
@@ -148,6 +181,8 @@ class Integrator:
         Dp = self._drift_params(ti_old, self.ti_current)
         self._update_scalars()
         self.sp.drift(Dp, self.P)
+        if statistics:
+            self.collect_statistics()
         info = self.sp.info()
         if info["dx_max"] > self.max_rel_dx * min(info["cell_width"]):
             self.sp.rebuild(self.P)
@@ -177,8 +212,8 @@ class Integrator:
                                            else min(old, r["min_new_bin"]))
         return self.result
 
-    def step(self) -> dict:
-        self.drift_to_next()
+    def step(self, statistics: bool = False) -> dict:
+        self.drift_to_next(statistics)
         self.forces()
         return self.end_step()
 
@@ -201,6 +236,17 @@ class _GravityDriver:
         self.potential_normalisation = 0.0
         self.mesh_ti_beg = self.mesh_ti_end = -1
         self.mesh_kicks = 0  # half mesh kicks given to the gparts so far
+        self.statistics = []  # (ti_current, finalised statistics) of the collected steps
+
+    def _stats_params(self, extrapolate: int = 1) -> abi.StatsParams:
+        """dt_kick_mesh_grav: from the middle of the mesh step that holds
+        ti_current to ti_current (engine_io.c:314-320)."""
+        dt_mesh = 0.0
+        if self.mesh and extrapolate and self.mesh_ti_end > 0:
+            mid = (self.mesh_ti_beg + self.mesh_ti_end) // 2
+            dt_mesh = (self.ti_current - mid) * self.time_base
+        return abi.StatsParams(self.ti_current, self.time_base, extrapolate, self.periodic,
+                               (self.box,) * 3, 1.0, 1.0, dt_mesh)
 
     def _gkick_params(self, dt_mesh: float = 0.0) -> abi.GKickParams:
         K = abi.GKickParams()
@@ -325,7 +371,12 @@ class NBodyIntegrator(_GravityDriver):
     _kick_params = _GravityDriver._gkick_params
 
     # -- the entry points -----------------------------------------------------
-    def init_step(self, gparts: np.ndarray) -> dict:
+    def collect_statistics(self, extrapolate: int = 1) -> dict:
+        st = lib.finalize_statistics(self.gs.statistics(self._stats_params(extrapolate)))
+        self.statistics.append((self.ti_current, st))
+        return st
+
+    def init_step(self, gparts: np.ndarray, statistics: bool = False) -> dict:
         """Upload the gparts (the only upload of the run), compute their first
         forces, time steps and half-kick. Live gparts start in time bin 0."""
         g = abi.copy_parts(gparts)
@@ -340,12 +391,15 @@ class NBodyIntegrator(_GravityDriver):
         self.gs.upload(g)
         self._build()
         self.gravity()
+        self.statistics = []
+        if statistics:
+            self.collect_statistics(extrapolate=0)
         self.gs.timestep(self.T)
         self.gs.kick1(self._kick_params(self._first_mesh_kick()))
         self.result = self.gs.step_result()
         return self.result
 
-    def drift_to_next(self) -> float:
+    def drift_to_next(self, statistics: bool = False) -> float:
         """Choose the next ti_current, drift there, rebuild the tree."""
         ti_old = self.ti_current
         self.ti_current = int(self.result["ti_end_min"])
@@ -355,6 +409,8 @@ class NBodyIntegrator(_GravityDriver):
         self._update_scalars()
         dt = (self.ti_current - ti_old) * self.time_base
         self.gs.drift(dt, self.periodic, (self.box,) * 3)
+        if statistics:
+            self.collect_statistics()
         self._build()
         return dt
 
@@ -364,8 +420,8 @@ class NBodyIntegrator(_GravityDriver):
         self.result = self.gs.step_result()
         return self.result
 
-    def step(self) -> dict:
-        self.drift_to_next()
+    def step(self, statistics: bool = False) -> dict:
+        self.drift_to_next(statistics)
         self.gravity()
         return self.end_step()
 
@@ -473,7 +529,21 @@ class CoupledIntegrator(_GravityDriver):
         self.sp.push_gparts(periodic=self.periodic, dim=(self.box,) * 3, **what)
 
     # -- the entry points -----------------------------------------------------
-    def init_step(self, parts: np.ndarray, xparts: np.ndarray, gparts: np.ndarray) -> dict:
+    def collect_statistics(self, extrapolate: int = 1) -> dict:
+        """Both sides queued, then both results: the gas sums from the space,
+        the dm sums and the gas's E_pot_self from the gspace."""
+        S = self._stats_params(extrapolate)
+        self.sp.statistics_enqueue(S)
+        self.gs.statistics_enqueue(S)
+        return self._read_statistics()
+
+    def _read_statistics(self) -> dict:
+        st = lib.finalize_statistics(self.sp.statistics_result(), self.gs.statistics_result())
+        self.statistics.append((self.ti_current, st))
+        return st
+
+    def init_step(self, parts: np.ndarray, xparts: np.ndarray, gparts: np.ndarray,
+                  statistics: bool = False) -> dict:
         """The only uploads of the run, then the first forces, time steps and
         half-kicks. Every live particle starts in time bin 0."""
         p, g = abi.copy_parts(parts), abi.copy_parts(gparts)
@@ -495,6 +565,9 @@ class CoupledIntegrator(_GravityDriver):
         self.gravity()
         self.sp.pull_gravity()
         self.chain = self.sp.hydro_step(self.P)
+        self.statistics = []
+        if statistics:
+            self.collect_statistics(extrapolate=0)
         self.sp.timestep_linked(self.T, self.P)
         self.gs.timestep(self.GT)
         self._push(time_bin=True)
@@ -509,7 +582,7 @@ class CoupledIntegrator(_GravityDriver):
         self.gs.kick1(self._gkick_params(dt_mesh))
         self._push(v_full=True)
 
-    def drift_to_next(self):
+    def drift_to_next(self, statistics: bool = False):
         """Choose the next ti_current, drift both sides there, hand the gas
         positions to the gas gparts, rebuild the tree. Returns (the space's
         abi.DriftParams, the time drifted)."""
@@ -522,11 +595,16 @@ class CoupledIntegrator(_GravityDriver):
         dt = (self.ti_current - ti_old) * self.time_base
         Dp = abi.DriftParams(dt, dt, dt, dt, self.min_u)
         self.sp.drift(Dp, self.P)
+        if statistics:  # before the rebuild voids the pulled accelerations
+            self.sp.statistics_enqueue(self._stats_params())
         info = self.sp.info()
         if info["dx_max"] > self.max_rel_dx * min(info["cell_width"]):
             self.sp.rebuild(self.P)
             self.rebuilds += 1
         self.gs.drift(dt, self.periodic, (self.box,) * 3)
+        if statistics:
+            self.gs.statistics_enqueue(self._stats_params())
+            self._read_statistics()
         self._push(x=True)
         self._build()
         return Dp, dt
@@ -568,8 +646,8 @@ class CoupledIntegrator(_GravityDriver):
                                            else min(old, r["min_new_bin"]))
         return self.result
 
-    def step(self) -> dict:
-        self.drift_to_next()
+    def step(self, statistics: bool = False) -> dict:
+        self.drift_to_next(statistics)
         self.forces()
         return self.end_step()
 

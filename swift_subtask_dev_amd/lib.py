@@ -66,6 +66,10 @@ HIP_SYMBOLS = [
     "swh_space_end_step_limited", "swh_space_limiter_result",
     "swh_space_limiter_loop_linked", "swh_space_limiter_apply_linked",
     "swh_space_end_step_limited_linked",
+    "swh_space_statistics", "swh_space_statistics_result", "swh_space_sync_velocities",
+    "swh_gspace_statistics", "swh_gspace_statistics_result", "swh_gspace_sync_velocities",
+    "swh_space_statistics_times", "swh_gspace_statistics_times",
+    "swh_statistics_add", "swh_statistics_finalize",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -228,6 +232,16 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
                                                         P(abi.TimestepParams), P(abi.KickParams),
                                                         P(abi.LimiterParams), P(abi.HydroParams),
                                                         dp, dp]),
+        "swh_space_statistics": (C.c_int, [vp, P(abi.StatsParams)]),
+        "swh_space_statistics_result": (C.c_int, [vp, P(abi.Statistics)]),
+        "swh_space_sync_velocities": (C.c_int, [vp, P(abi.StatsParams), vp, C.c_int]),
+        "swh_gspace_statistics": (C.c_int, [vp, P(abi.StatsParams)]),
+        "swh_gspace_statistics_result": (C.c_int, [vp, P(abi.Statistics)]),
+        "swh_gspace_sync_velocities": (C.c_int, [vp, P(abi.StatsParams), vp, C.c_int]),
+        "swh_space_statistics_times": (C.c_int, [vp, P(C.c_float)]),
+        "swh_gspace_statistics_times": (C.c_int, [vp, P(C.c_float)]),
+        "swh_statistics_add": (None, [P(abi.Statistics), P(abi.Statistics)]),
+        "swh_statistics_finalize": (None, [P(abi.Statistics)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -300,6 +314,22 @@ def _check(status: int, where: str, lib: C.CDLL | None = None) -> None:
     if status != 0:
         detail = ((lib or load()).swh_last_error() or b"").decode(errors="replace")
         raise SwhError(status, where, detail)
+
+
+def finalize_statistics(*parts: dict) -> dict:
+    """The sum of per-object statistics dicts (HydroSpace.statistics,
+    GravSpace.statistics; swh_statistics_add), finalised as stats_finalize
+    does: total_mass = gas + dm, com = sum m x / total_mass. E_tot = E_kin +
+    E_int + E_pot_self is added for convenience."""
+    L = load()
+    tot = abi.Statistics()
+    for d in parts:
+        L.swh_statistics_add(C.byref(tot), C.byref(abi.Statistics.from_dict(d)))
+    L.swh_statistics_finalize(C.byref(tot))
+    out = tot.as_dict()
+    out["total_mass"] = out["gas_mass"] + out["dm_mass"]
+    out["E_tot"] = out["E_kin"] + out["E_int"] + out["E_pot_self"]
+    return out
 
 
 def part_layout() -> abi.PartLayout:
@@ -653,6 +683,44 @@ class HydroSpace:
         _check(self._lib.swh_space_link_times(self.handle, ms), "link_times", self._lib)
         return dict(zip(("pull", "push", "end_step"), map(float, ms)))
 
+    # ---- statistics and snapshot velocities (swh_stats.hip) ---------------
+    def statistics_enqueue(self, S: abi.StatsParams):
+        """Queue stats_collect over the owned, live particles (no host wait)."""
+        _check(self._lib.swh_space_statistics(self.handle, C.byref(S)), "statistics", self._lib)
+
+    def statistics_result(self) -> dict:
+        """Wait for the last statistics_enqueue; partial sums (com = sum m x)."""
+        r = abi.Statistics()
+        _check(self._lib.swh_space_statistics_result(self.handle, C.byref(r)),
+               "statistics_result", self._lib)
+        return r.as_dict()
+
+    def statistics(self, S: abi.StatsParams) -> dict:
+        self.statistics_enqueue(S)
+        return self.statistics_result()
+
+    def sync_velocities(self, S: abi.StatsParams, out_ptr: int = None) -> np.ndarray:
+        """The snapshot velocity of every particle (convert_part_vel): n x 3
+        float32, caller order; 0 for inhibited and foreign particles. out_ptr:
+        a device buffer of that size to write instead (returns None)."""
+        if out_ptr is not None:
+            _check(self._lib.swh_space_sync_velocities(self.handle, C.byref(S),
+                                                       C.c_void_p(out_ptr), 1),
+                   "sync_velocities", self._lib)
+            return None
+        out = np.zeros((self._lib.swh_space_count(self.handle), 3), dtype=np.float32)
+        _check(self._lib.swh_space_sync_velocities(self.handle, C.byref(S), _ptr(out), 0),
+               "sync_velocities", self._lib)
+        return out
+
+    def statistics_ms(self) -> dict:
+        """HIP-event times (ms) of the last statistics and sync_velocities
+        launches (-1: not run)."""
+        ms = (C.c_float * 2)()
+        _check(self._lib.swh_space_statistics_times(self.handle, ms), "statistics_times",
+               self._lib)
+        return dict(zip(("statistics", "sync_velocities"), map(float, ms)))
+
     def hydro_step(self, P):
         """The full SPHENIX hydro chain of one step:
         density -> ghost -> gradient -> extra ghost -> force -> end force."""
@@ -861,6 +929,43 @@ class GravSpace:
         ms = (C.c_float * 4)()
         _check(self._lib.swh_gspace_step_times(self.handle, ms), "step_times", self._lib)
         return dict(zip(("drift", "init_grav", "end_force", "end_step"), map(float, ms)))
+
+    # ---- statistics and snapshot velocities (swh_stats.hip) ---------------
+    def statistics_enqueue(self, S: abi.StatsParams):
+        """Queue stats_collect over the stored records (no host wait): the dm
+        sums, and E_pot_self of the gas from the gas gparts."""
+        _check(self._lib.swh_gspace_statistics(self.handle, C.byref(S)), "gspace_statistics",
+               self._lib)
+
+    def statistics_result(self) -> dict:
+        r = abi.Statistics()
+        _check(self._lib.swh_gspace_statistics_result(self.handle, C.byref(r)),
+               "gspace_statistics_result", self._lib)
+        return r.as_dict()
+
+    def statistics(self, S: abi.StatsParams) -> dict:
+        self.statistics_enqueue(S)
+        return self.statistics_result()
+
+    def sync_velocities(self, S: abi.StatsParams, out_ptr: int = None) -> np.ndarray:
+        """The snapshot velocity of every gpart (convert_gpart_vel): n x 3
+        float32 in record order (as download); 0 for inhibited gparts. out_ptr:
+        a device buffer of that size to write instead (returns None)."""
+        if out_ptr is not None:
+            _check(self._lib.swh_gspace_sync_velocities(self.handle, C.byref(S),
+                                                        C.c_void_p(out_ptr), 1),
+                   "gspace_sync_velocities", self._lib)
+            return None
+        out = np.zeros((getattr(self, "_n", 0), 3), dtype=np.float32)
+        _check(self._lib.swh_gspace_sync_velocities(self.handle, C.byref(S), _ptr(out), 0),
+               "gspace_sync_velocities", self._lib)
+        return out
+
+    def statistics_ms(self) -> dict:
+        ms = (C.c_float * 2)()
+        _check(self._lib.swh_gspace_statistics_times(self.handle, ms), "gspace_statistics_times",
+               self._lib)
+        return dict(zip(("statistics", "sync_velocities"), map(float, ms)))
 
     def sync(self):
         _check(self._lib.swh_gspace_sync(self.handle), "gspace_sync", self._lib)
