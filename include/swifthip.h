@@ -45,7 +45,8 @@ extern "C" {
 #endif
 
 /* v15 also gained, without a new number (purely additive: no struct or
- * signature moved), the statistics entries at the end of this header. */
+ * signature moved), the statistics entries at the end of this header, and
+ * after them swh_gspace_drift_softened and the displacement-constraint sums. */
 #define SWH_ABI_VERSION 15
 
 #if defined(__GNUC__)
@@ -834,7 +835,8 @@ SWH_API swh_status swh_gspace_pm_mesh(swh_gspace *g, const swh_pm_params *M,
 /* a counterpart -- type dark matter (1), DM background (2), neutrino  */
 /* (6), src/part_type.h:28-34 -- are kicked and time-stepped (kick1    */
 /* tests the new bin: gpart_is_starting). gravity_predict_extra (the   */
-/* softening update) is not applied: epsilon stays as uploaded. The    */
+/* softening update) is applied by swh_gspace_drift_softened only:     */
+/* after swh_gspace_drift epsilon stays as it was. The                 */
 /* calls only enqueue on the gspace's stream. Each returns             */
 /* SWH_ERR_STATE before swh_gspace_upload or before                    */
 /* swh_gspace_set_step_layout, and is a no-op for an empty set.        */
@@ -868,6 +870,27 @@ typedef struct swh_gdrift_params {
  * geometry); their multipoles must be made again before the next allow_mpole
  * batch. */
 SWH_API swh_status swh_gspace_drift(swh_gspace *g, const swh_gdrift_params *D);
+
+/* gravity_props' current softenings (src/gravity_properties.c:259-290), as
+ * the kernels use them: 3 x the Plummer-equivalent length. */
+typedef struct swh_gsoftening_params {
+  float epsilon_DM_cur, epsilon_baryon_cur, epsilon_nu_cur, epsilon_background_fac;
+} swh_gsoftening_params;
+/* swh_gspace_drift and, in the same pass, gravity_predict_extra
+ * (src/gravity/MultiSoftening/gravity.h:294-325, called from drift_gpart,
+ * src/drift.h:102-107): every gpart that is not inhibited is drifted and then
+ * gets the softening of its type -- dark matter (1) epsilon_DM_cur; gas, sink,
+ * stars, black hole (0, 3, 4, 5) epsilon_baryon_cur; DM background (2)
+ * epsilon_background_fac * cbrt(mass); neutrino (6) epsilon_nu_cur; any other
+ * type keeps its own. The same state rules as swh_gspace_drift. dt_drift = 0
+ * is legal and leaves x bit-identical (the first softening of a run, as
+ * gravity_first_init_gpart). swh_grav_pp_batch, swh_grav_tree and
+ * swh_gspace_grav_down pack (x, epsilon) and 1 / epsilon from the records at
+ * the start of every call, and the multipoles (with their largest softening)
+ * are made again after any drift, so the next gravity call uses the new
+ * softening. */
+SWH_API swh_status swh_gspace_drift_softened(swh_gspace *g, const swh_gdrift_params *D,
+                                             const swh_gsoftening_params *S);
 
 /* a_grav = 0, potential = 0 in the records of the active gparts; their
  * accumulators are cleared too. */
@@ -1129,6 +1152,55 @@ SWH_API swh_status swh_gspace_statistics_times(swh_gspace *g, float *ms);
  * com /= total mass when it is positive (stats_finalize, statistics.c:678). */
 SWH_API void swh_statistics_add(swh_statistics *a, const swh_statistics *b);
 SWH_API void swh_statistics_finalize(swh_statistics *a);
+
+/* ------------------------------------------------------------------ */
+/* The sums of the RMS-displacement constraint (added to ABI v15;      */
+/* purely additive): what space_parts_get_cell_index and               */
+/* space_gparts_get_cell_index collect at a rebuild                    */
+/* (src/space_cell_index.c:141-181, 267-313), on the device, and       */
+/* engine_recompute_displacement_constraint's cosmological half        */
+/* (src/engine.c:3384-3509) on the host.                               */
+/* ------------------------------------------------------------------ */
+typedef struct swh_displacement_sums {
+  double sum_vel_norm; /* sum of (float)(v0*v0 + v1*v1 + v2*v2) */
+  float min_mass;      /* FLT_MAX when nothing was counted */
+  int32_t reserved;
+  int64_t count;
+} swh_displacement_sums;
+/* Over the space's own particles that are neither inhibited nor
+ * not-yet-created: p->v (the drifted velocity, not v_full) and the hydro mass.
+ * Each term is a float, evaluated left to right; the terms are added in double
+ * the way swh_space_statistics adds its own (no floating-point atomics: the
+ * same state gives the same bits on every call). One launch and a one-wave
+ * reduction on the space's stream, the result copied to pinned host memory
+ * behind them; no host wait. Nothing is written to a particle, no list is
+ * dropped. SWH_ERR_STATE before swh_space_upload_xparts / _rebuild. */
+SWH_API swh_status swh_space_displacement_sums(swh_space *s);
+/* Waits for the last swh_space_displacement_sums; SWH_ERR_STATE if there was
+ * none. An empty space gives {0, FLT_MAX, 0, 0}. */
+SWH_API swh_status swh_space_displacement_sums_result(swh_space *s, swh_displacement_sums *out);
+/* The same over the stored records of a gspace (after swh_gspace_upload and
+ * swh_gspace_set_step_layout): dark-matter gparts (type 1) only, v_full and
+ * mass. The tree is not made stale. */
+SWH_API swh_status swh_gspace_displacement_sums(swh_gspace *g);
+SWH_API swh_status swh_gspace_displacement_sums_result(swh_gspace *g, swh_displacement_sums *out);
+
+typedef struct swh_rms_params {
+  float Omega_cdm, Omega_b, H0, a, const_G;
+  float r_s;                         /* mesh->r_s; FLT_MAX without a periodic mesh */
+  float max_RMS_displacement_factor; /* SWIFT's default 0.25 */
+  int32_t use_only_gas;              /* no other baryon species exists here; kept for the ABI */
+} swh_rms_params;
+/* Host only. e->dt_max_RMS_displacement in the reference's float arithmetic:
+ * per species a * a * min(r_s, cbrt(min_mass / (Omega * rho_crit0))) /
+ * sqrt(sum_vel_norm / count), the smaller of the two times the factor. A
+ * double sum is rounded to float once, where the reference holds its float
+ * sum. A species with count == 0 or a NULL pointer gives FLT_MAX for its term.
+ * The cube root is the library's own IEEE-only one (as the softening of the
+ * background type), not the C library's. */
+SWH_API float swh_dt_max_rms_displacement(const swh_rms_params *R,
+                                          const swh_displacement_sums *gas,
+                                          const swh_displacement_sums *dm);
 
 #ifdef __cplusplus
 }

@@ -348,6 +348,42 @@ class GDriftParams(C.Structure):
         super().__init__(dt_drift, int(periodic), 0, (C.c_double * 3)(*dim))
 
 
+class GSofteningParams(C.Structure):
+    """swh_gsoftening_params: gravity_props' current softenings, as the kernels
+    use them (3 x the Plummer-equivalent length; cosmo.softening_cur)."""
+
+    _fields_ = [(n, C.c_float) for n in ("epsilon_DM_cur", "epsilon_baryon_cur",
+                                         "epsilon_nu_cur", "epsilon_background_fac")]
+
+
+class DisplacementSums(C.Structure):
+    """swh_displacement_sums: one species' sums of the RMS-displacement
+    constraint."""
+
+    _fields_ = [("sum_vel_norm", C.c_double), ("min_mass", C.c_float), ("reserved", C.c_int32),
+                ("count", C.c_int64)]
+
+    def __init__(self, sum_vel_norm=0.0, min_mass=np.finfo(np.float32).max, count=0):
+        super().__init__(float(sum_vel_norm), float(min_mass), 0, int(count))
+
+    def as_dict(self) -> dict:
+        return {"sum_vel_norm": float(self.sum_vel_norm), "min_mass": np.float32(self.min_mass),
+                "count": int(self.count)}
+
+
+class RmsParams(C.Structure):
+    """swh_rms_params: the scalars of engine_recompute_displacement_constraint."""
+
+    _fields_ = [(n, C.c_float) for n in ("Omega_cdm", "Omega_b", "H0", "a", "const_G", "r_s",
+                                         "max_RMS_displacement_factor")] + [
+                                             ("use_only_gas", C.c_int32)]
+
+    def __init__(self, Omega_cdm=0.0, Omega_b=0.0, H0=0.0, a=1.0, const_G=1.0,
+                 r_s=np.finfo(np.float32).max, max_RMS_displacement_factor=0.25, use_only_gas=0):
+        super().__init__(Omega_cdm, Omega_b, H0, a, const_G, r_s, max_RMS_displacement_factor,
+                         int(use_only_gas))
+
+
 class GEndParams(C.Structure):
     """swh_gend_params."""
 

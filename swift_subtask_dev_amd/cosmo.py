@@ -167,6 +167,48 @@ def kick_tables(cosmo: Cosmology, ti_current: int, kick: int) -> dict:
     return out
 
 
+def _kick_integrals(cosmo: Cosmology, ti_beg: np.ndarray, ti_end: np.ndarray,
+                    power: float) -> np.ndarray:
+    """_kick_integral over many intervals at once: one row of 32 nodes per
+    interval, every row evaluated and added exactly as the scalar function
+    does, so each value has the same bits."""
+    lo = (cosmo.log_a_begin + ti_beg * cosmo.time_base)[:, None]
+    hi = (cosmo.log_a_begin + ti_end * cosmo.time_base)[:, None]
+    xg, wg = np.polynomial.legendre.leggauss(32)
+    a = np.exp(lo + 0.5 * (hi - lo) * (xg + 1.0))
+    return (0.5 * (hi - lo) * wg / (cosmo.H(a) * a ** power)).sum(axis=1)
+
+
+def kick_tables_active(cosmo: Cosmology, ti_current: int, kick: int, max_active_bin: int) -> dict:
+    """kick_tables for the bins a kick at ti_current can read, 1..max_active_bin
+    (a particle is kicked only when its step ends or starts at ti_current, and
+    a new bin's step divides ti_current, so no higher bin is looked up); the
+    entries above stay zero. Vectorised over the bins: three numpy passes in
+    place of 3 x 56 small ones, the same bits in every bin it fills."""
+    out = {k: np.zeros(NUM_TIME_BINS + 1) for k in ("hydro", "grav", "therm")}
+    bins = np.arange(1, min(int(max_active_bin), NUM_TIME_BINS) + 1)
+    half = np.array([get_integer_timestep(int(b)) // 2 for b in bins], dtype=np.int64)
+    lo, hi = (ti_current - half, ti_current + 0 * half) if kick == 2 else (
+        ti_current + 0 * half, ti_current + half)
+    ok = (lo >= 0) & (hi <= MAX_NR_TIMESTEPS)  # the others: no such step on the time line
+    if ok.any():
+        for k, p in (("grav", 1.0), ("hydro", 3.0 * (HYDRO_GAMMA - 1.0)), ("therm", 2.0)):
+            out[k][bins[ok]] = _kick_integrals(cosmo, lo[ok], hi[ok], p)
+    return out
+
+
+def softening_cur(comoving: float, max_physical: float, a: float) -> np.float32:
+    """gravity_props_update (src/gravity_properties.c:259-290) for one species:
+    the softening the kernels use at scale factor a, from its comoving and its
+    maximal physical Plummer-equivalent lengths. Comoving until comoving * a
+    exceeds max_physical, then max_physical / a; times
+    kernel_gravity_softening_plummer_equivalent = 3. The two lengths are floats
+    in gravity_props, the arithmetic is in double and the result a float."""
+    comoving, max_physical = float(np.float32(comoving)), float(np.float32(max_physical))
+    eps = max_physical / a if comoving * a > max_physical else comoving
+    return np.float32(eps * 3.0)
+
+
 def limiter_tables(cosmo: Cosmology, ti_current: int) -> tuple:
     """swh_limiter_params' per-bin kick intervals at ti_current with cosmology
     (timestep_limit_part, src/timestep_limiter.h:137-204), from the integrals

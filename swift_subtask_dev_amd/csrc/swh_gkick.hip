@@ -1,6 +1,7 @@
 // swh_gkick.hip — the gpart stages of a device-resident N-body step on a
-// gspace: the drift, gravity_init_gpart, runner_do_end_grav_force and the
-// gpart loops of
+// gspace: the drift (with gravity_predict_extra's softening update when asked:
+// swh_gspace_drift_softened), gravity_init_gpart, runner_do_end_grav_force and
+// the gpart loops of
 //   runner_do_kick2    (src/runner_time_integration.c:482-520)
 //   runner_do_timestep (:841-900)
 //   runner_do_kick1    (:210-250)
@@ -21,8 +22,8 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "swh_internal.h"  // first: the HIP runtime's device memcpy, for swh_stats.h
 #include "swh_gstep.h"
-#include "swh_internal.h"
 #include "swh_physics.h"
 #include "swh_steprec.h"
 #include "swh_timeline.h"
@@ -117,15 +118,42 @@ struct GRec {
   }
 };
 
-template <bool STD>
+// The softenings of a softened drift and where a record keeps its mass (the
+// background type's softening needs it).
+struct GSoftDev {
+  GSoftening S;
+  int mass;
+};
+
+// SOFT: gravity_predict_extra after the drift (src/drift.h:102-107). A
+// softened drift over dt_drift == 0 (the first softening of a run) does not
+// touch x, so not even a -0. changes its bits.
+template <bool STD, bool SOFT = false>
 __global__ __launch_bounds__(256) void gdrift_kernel(GStepLayout L, char* __restrict__ aos,
                                                      int64_t n, double dt_drift, int periodic,
-                                                     double dim0, double dim1, double dim2) {
+                                                     double dim0, double dim1, double dim2,
+                                                     GSoftDev soft) {
   const double dim[3] = {dim0, dim1, dim2};
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
        s += (int64_t)gridDim.x * blockDim.x) {
     char* r = aos + s * L.stride;
     if (*reinterpret_cast<const int8_t*>(r + L.time_bin) == kTimeBinInhibited) continue;
+    if (SOFT) {
+      if (STD) {
+        // bytes 80..96: old_a_grav_norm, epsilon, {time_bin, type, pad}, pad
+        float4 q3 = *reinterpret_cast<const float4*>(r + 80);
+        const int type = (int)(int8_t)((__float_as_int(q3.z) >> 8) & 0xff);
+        const float m = type == 2 ? *reinterpret_cast<const float*>(r + 76) : 0.f;
+        q3.y = gravity_predict_extra(type, m, q3.y, soft.S);
+        *reinterpret_cast<float4*>(r + 80) = q3;
+      } else {
+        const int type = *reinterpret_cast<const int8_t*>(r + L.type);
+        const float m = type == 2 ? *reinterpret_cast<const float*>(r + soft.mass) : 0.f;
+        float* e = reinterpret_cast<float*>(r + L.epsilon);
+        *e = gravity_predict_extra(type, m, *e, soft.S);
+      }
+      if (dt_drift == 0.) continue;
+    }
     float v[3];
     if (STD) {
       const float4 q = *reinterpret_cast<const float4*>(r + 32);
@@ -392,32 +420,59 @@ swh_status swh_gspace_set_step_layout(swh_gspace* g, const swh_gpart_step_layout
   return SWH_OK;
 }
 
-swh_status swh_gspace_drift(swh_gspace* g, const swh_gdrift_params* D) {
-  if (!g || !D) return SWH_ERR_ARG;
+// S: the softened drift's softenings (NULL: swh_gspace_drift)
+static swh_status launch_gdrift(swh_gspace* g, const swh_gdrift_params* D,
+                                const swh_gsoftening_params* S, const char* what) {
   if (D->periodic && !(D->dim[0] > 0. && D->dim[1] > 0. && D->dim[2] > 0.)) {
-    set_error("swh_gspace_drift: a periodic box needs dim > 0");
+    set_error("%s: a periodic box needs dim > 0", what);
     return SWH_ERR_ARG;
   }
-  SWH_TRY(step_ready(g, "swh_gspace_drift"));
+  SWH_TRY(step_ready(g, what));
   if (g->n == 0) return SWH_OK;
-  SWH_HIP(hipSetDevice(g->ctx->device));
   const GStepLayout L = step_layout_of(g);
+  GSoftDev soft{};
+  if (S) {
+    soft.S = GSoftening{S->epsilon_DM_cur, S->epsilon_baryon_cur, S->epsilon_nu_cur,
+                        S->epsilon_background_fac};
+    soft.mass = g->layout.mass;
+    if (!float_field_ok(soft.mass, 1, L.stride)) {
+      set_error("%s: mass of the uploaded gpart layout must lie inside the record of %d bytes, "
+                "4-byte aligned", what, L.stride);
+      return SWH_ERR_ARG;
+    }
+  }
+  SWH_HIP(hipSetDevice(g->ctx->device));
   const int grid = gstep_grid(g->n);
+  const bool std_rec = is_std_layout(L, g->aos.ptr) && (!S || soft.mass == 76);
   SWH_TRY(g->gstep_timer.begin(GT_DRIFT, g->stream));
-  if (is_std_layout(L, g->aos.ptr))
-    hipLaunchKernelGGL(gdrift_kernel<true>, dim3(grid), dim3(256), 0, g->stream, L,
-                       g->aos.as<char>(), g->n, D->dt_drift, D->periodic, D->dim[0], D->dim[1],
-                       D->dim[2]);
-  else
-    hipLaunchKernelGGL(gdrift_kernel<false>, dim3(grid), dim3(256), 0, g->stream, L,
-                       g->aos.as<char>(), g->n, D->dt_drift, D->periodic, D->dim[0], D->dim[1],
-                       D->dim[2]);
+#define SWH_GDRIFT(STD, SOFT)                                                                    \
+  hipLaunchKernelGGL((gdrift_kernel<STD, SOFT>), dim3(grid), dim3(256), 0, g->stream, L,         \
+                     g->aos.as<char>(), g->n, D->dt_drift, D->periodic, D->dim[0], D->dim[1],    \
+                     D->dim[2], soft)
+  if (std_rec) {
+    if (S) SWH_GDRIFT(true, true); else SWH_GDRIFT(true, false);
+  } else {
+    if (S) SWH_GDRIFT(false, true); else SWH_GDRIFT(false, false);
+  }
+#undef SWH_GDRIFT
   SWH_HIP(hipGetLastError());
   SWH_TRY(g->gstep_timer.end(GT_DRIFT, g->stream));
-  // the cells' geometry no longer bounds their gparts
+  // the cells' geometry no longer bounds their gparts (and, softened, the
+  // cells' largest softening is no longer the gparts')
   g->mpoles_valid = false;
   g->tree_stale = true;
   return SWH_OK;
+}
+
+swh_status swh_gspace_drift(swh_gspace* g, const swh_gdrift_params* D) {
+  if (!g || !D) return SWH_ERR_ARG;
+  return launch_gdrift(g, D, nullptr, "swh_gspace_drift");
+}
+
+swh_status swh_gspace_drift_softened(swh_gspace* g, const swh_gdrift_params* D,
+                                     const swh_gsoftening_params* S) {
+  if (!g || !D || !S) return SWH_ERR_ARG;
+  return launch_gdrift(g, D, S, "swh_gspace_drift_softened");
 }
 
 swh_status swh_gspace_init_grav(swh_gspace* g, int32_t max_active_bin) {

@@ -7,16 +7,17 @@
 //   kick_gpart                    src/kick.h:180-187
 //   gravity_compute_timestep_self gravity.h:141-172 (a_hydro = 0)
 //   get_gpart_timestep            src/timestep.h:91-131
+//   gravity_predict_extra         gravity.h:294-325 (the drift's softening update)
 // The device kernels (swh_gkick.hip) call them on registers, a plain host
-// program (tests/test_gstep_host.py) on the CPU. No HIP header is needed to
-// include this file. gravity_predict_extra (the softening update of the
-// drift) is not restated: epsilon stays as uploaded.
+// program (tests/test_gstep_host.py, tests/test_cosmo_run_host.py) on the CPU.
+// No HIP header is needed to include this file.
 #pragma once
 
 #include <float.h>
 #include <math.h>
 #include <stdint.h>
 
+#include "swh_stats.h"  // stats_cbrtf
 #include "swh_timeline.h"
 
 // a * b + c stays two roundings, as the gcc-built reference evaluates it
@@ -52,6 +53,34 @@ SWH_HD void drift_gpart(double x[3], const float v_full[3], double dt_drift, int
     double xk = x[k] + (double)v_full[k] * dt_drift;
     if (periodic) xk = xk < 0. ? xk + dim[k] : (xk >= dim[k] ? xk - dim[k] : xk);
     x[k] = xk;
+  }
+}
+
+// gravity_props' current softenings (internal lengths: 3 x Plummer), as
+// swh_gsoftening_params
+struct GSoftening {
+  float epsilon_DM_cur, epsilon_baryon_cur, epsilon_nu_cur, epsilon_background_fac;
+};
+
+// The softening a gpart of `type` carries after a drift. The cube root of a
+// background particle's mass is stats_cbrtf, not the C library's cbrtf: only
+// IEEE operations, so the host, the device and numpy give the same bits. A
+// type the switch does not name keeps its softening.
+SWH_HD float gravity_predict_extra(int type, float mass, float epsilon, const GSoftening& S) {
+  switch (type) {
+    case 1:  // dark matter
+      return S.epsilon_DM_cur;
+    case 0:  // gas
+    case 3:  // sink
+    case 4:  // stars
+    case 5:  // black hole
+      return S.epsilon_baryon_cur;
+    case 2:  // DM background
+      return S.epsilon_background_fac * stats_cbrtf(mass);
+    case 6:  // neutrino
+      return S.epsilon_nu_cur;
+    default:
+      return epsilon;
   }
 }
 

@@ -182,6 +182,26 @@ struct StatsState {
   ~StatsState() { release(); }  // with its space (swh_space_destroy's delete)
 };
 
+// The displacement-constraint sums of a space or a gspace (swh_rms.hip), host
+// side: the blocks' partial records, the reduced record, its pinned copy and
+// the event behind the last copy.
+struct RmsState {
+  DevBuf partials, out;
+  HostBuf host;
+  hipEvent_t event = nullptr;
+  bool pending = false;  // a copy is queued and not yet waited for
+  bool has = false;      // host holds the result of some call
+  void release() {
+    partials.release();
+    out.release();
+    host.release();
+    if (event) (void)hipEventDestroy(event);
+    event = nullptr;
+    pending = has = false;
+  }
+  ~RmsState() { release(); }  // with its space (the destroy calls' delete)
+};
+
 // Device copy of the AoS layout (offsets), passed by value to kernels.
 struct Layout {
   int stride;
@@ -315,6 +335,7 @@ struct swh_space {
   // the last pull, push and linked kick / timestep launch (swh_space_link_times)
   swh::StageTimer<3> link_timer;
   swh::StatsState stats;  // swh_space_statistics / _sync_velocities (swh_stats.hip)
+  swh::RmsState rms;      // swh_space_displacement_sums (swh_rms.hip)
   // grid
   swh::DevBuf cell_start;  // int32[ncell+1], indexed by Morton rank
   swh::DevBuf cell_rank;   // int32[ncell]: linear cell -> Morton rank
@@ -450,6 +471,7 @@ struct swh_gspace {
   swh_space* link = nullptr;
   hipEvent_t link_event = nullptr;  // recorded on this gspace's stream for the space's
   swh::StatsState stats;  // swh_gspace_statistics / _sync_velocities (swh_stats.hip)
+  swh::RmsState rms;      // swh_gspace_displacement_sums (swh_rms.hip)
 };
 
 namespace swh {

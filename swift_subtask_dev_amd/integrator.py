@@ -36,6 +36,9 @@ Non-cosmological by default (time_base = the physical time of one tick of the
 integer time line). With a cosmo.Cosmology the time line runs in log a: the
 drift and kick factors are the integrals of cosmo.kick_tables, the engine
 scalars follow cosmology_update, and min_u is the comoving floor.
+NBodyIntegrator and CoupledIntegrator take cosmology= too (their docstrings):
+the gparts' drift then carries the softening update, the kicks the integrals of
+dt / a, and the RMS-displacement constraint bounds the steps and the mesh step.
 """
 from __future__ import annotations
 
@@ -54,6 +57,35 @@ def get_max_active_bin(ti: int) -> int:
     while not ((1 << (b + 1)) & ti):
         b += 1
     return b
+
+
+def _cosmo_gas_scalars(cm, ti_current: int, P: abi.HydroParams, T: abi.TimestepParams) -> float:
+    """The gas side's engine scalars of a cosmological step at ti_current
+    (cosmology_update, cosmology.c:225-295). Returns a."""
+    a = cm.scale_factor(ti_current)
+    g = cosmo_mod.HYDRO_GAMMA
+    P.a = a
+    P.H = float(cm.H(a))
+    P.a2_inv = 1.0 / (a * a)
+    P.a_factor_sound_speed = a ** (-1.5 * (g - 1.0))
+    P.a_factor_Balsara_eps = a ** (0.5 * (1.0 - 3.0 * g))
+    P.set_dt_alpha_bins(cosmo_mod.dt_alpha_table(cm, ti_current))
+    T.time_step_factor = P.H          # cosmology.c:295
+    T.a_factor_grav_accel = 1.0 / (a * a)  # cosmology.c:243-245
+    T.a_factor_hydro_accel = a ** (-3.0 * g + 2.0)
+    return a
+
+
+def _gas_drift_params(cm, ti_old: int, ti_new: int, time_base: float,
+                      min_u: float) -> abi.DriftParams:
+    """The four factors of a gas drift from ti_old to ti_new."""
+    if cm is None:
+        dt = (ti_new - ti_old) * time_base
+        return abi.DriftParams(dt, dt, dt, dt, min_u)
+    g = cosmo_mod.HYDRO_GAMMA
+    ki = cosmo_mod._kick_integral
+    return abi.DriftParams(ki(cm, ti_old, ti_new, 2.0), ki(cm, ti_old, ti_new, 3.0 * (g - 1.0)),
+                           ki(cm, ti_old, ti_new, 1.0), ki(cm, ti_old, ti_new, 2.0), min_u)
 
 
 class Integrator:
@@ -85,20 +117,8 @@ class Integrator:
     def _update_scalars(self):
         self.P.max_active_bin = self.max_active_bin
         self.T.ti_current = self.ti_current
-        cm = self.cosmology
-        if cm is None:
-            return
-        a = cm.scale_factor(self.ti_current)
-        g = cosmo_mod.HYDRO_GAMMA
-        self.P.a = a
-        self.P.H = float(cm.H(a))
-        self.P.a2_inv = 1.0 / (a * a)
-        self.P.a_factor_sound_speed = a ** (-1.5 * (g - 1.0))
-        self.P.a_factor_Balsara_eps = a ** (0.5 * (1.0 - 3.0 * g))
-        self.P.set_dt_alpha_bins(cosmo_mod.dt_alpha_table(cm, self.ti_current))
-        self.T.time_step_factor = self.P.H          # cosmology.c:295
-        self.T.a_factor_grav_accel = 1.0 / (a * a)  # cosmology.c:243-245
-        self.T.a_factor_hydro_accel = a ** (-3.0 * g + 2.0)
+        if self.cosmology is not None:
+            _cosmo_gas_scalars(self.cosmology, self.ti_current, self.P, self.T)
 
     def _kick_params(self, kick: int) -> abi.KickParams:
         K = abi.KickParams()
@@ -121,15 +141,7 @@ class Integrator:
         return L
 
     def _drift_params(self, ti_old: int, ti_new: int) -> abi.DriftParams:
-        cm = self.cosmology
-        if cm is None:
-            dt = (ti_new - ti_old) * self.time_base
-            return abi.DriftParams(dt, dt, dt, dt, self.min_u)
-        g = cosmo_mod.HYDRO_GAMMA
-        ki = cosmo_mod._kick_integral
-        return abi.DriftParams(ki(cm, ti_old, ti_new, 2.0), ki(cm, ti_old, ti_new, 3.0 * (g - 1.0)),
-                               ki(cm, ti_old, ti_new, 1.0), ki(cm, ti_old, ti_new, 2.0),
-                               self.min_u)
+        return _gas_drift_params(self.cosmology, ti_old, ti_new, self.time_base, self.min_u)
 
     def _stats_params(self, extrapolate: int = 1) -> abi.StatsParams:
         dim = tuple(self.P.dim)
@@ -225,10 +237,30 @@ class Integrator:
 
 class _GravityDriver:
     """What NBodyIntegrator and CoupledIntegrator share on the gspace side: the
-    tree build, the gravity stages and the mesh schedule of engine.c:3528-3550
-    without the RMS-displacement term. Expects gs, G, GT (abi.GTimestepParams),
-    time_base, cdim, split_size, max_depth, box, const_G, mesh, periodic,
-    ti_current and max_active_bin on the object."""
+    tree build, the gravity stages, the mesh schedule of engine.c:3528-3550 and,
+    with a cosmology, the factors of a run in log a: the drift's integral of
+    dt / a^2 with the softening of gravity_props_update at the new a, the
+    per-bin and the mesh kick integrals of dt / a, and the RMS-displacement
+    constraint (engine_recompute_displacement_constraint) from the sums the
+    device collects where a mesh step ends. Expects gs, G, GT
+    (abi.GTimestepParams), time_base, cdim, split_size, max_depth, box,
+    const_G, mesh, periodic, ti_current and max_active_bin on the object."""
+
+    def _init_cosmology(self, cosmology, time_base, softening, max_rms_displacement_factor):
+        """time_base of the run: the cosmology's (log a per tick), or the
+        caller's physical time per tick."""
+        if cosmology is None and (not time_base or time_base <= 0):
+            raise ValueError("time_base (time per tick) must be positive")
+        if cosmology is not None and softening is None:
+            raise ValueError("a cosmological run needs softening= (the comoving and the maximal "
+                             "physical Plummer-equivalent lengths)")
+        self.cosmology = cosmology
+        self.softening = dict(softening) if softening else None
+        self.max_rms_displacement_factor = float(max_rms_displacement_factor)
+        self.dt_max_rms = float(np.finfo(np.float32).max)  # e->dt_max_RMS_displacement
+        self._rms_pending = False
+        self._tables = {}
+        return cosmology.time_base if cosmology is not None else float(time_base)
 
     def _reset_gravity(self):
         self.tops = None
@@ -237,6 +269,104 @@ class _GravityDriver:
         self.mesh_ti_beg = self.mesh_ti_end = -1
         self.mesh_kicks = 0  # half mesh kicks given to the gparts so far
         self.statistics = []  # (ti_current, finalised statistics) of the collected steps
+        self.dt_max_rms = float(np.finfo(np.float32).max)
+        self._rms_pending = False
+
+    # -- cosmological factors ---------------------------------------------
+    def _softening_params(self, a: float) -> abi.GSofteningParams:
+        """gravity_props_update at scale factor a. softening: dm_comoving,
+        dm_max_physical, baryon_comoving, baryon_max_physical (Plummer
+        equivalent), optionally nu_comoving / nu_max_physical (the dark
+        matter's otherwise) and background_fac (0)."""
+        s = self.softening
+        cur = cosmo_mod.softening_cur
+        dm = cur(s["dm_comoving"], s["dm_max_physical"], a)
+        return abi.GSofteningParams(
+            dm, cur(s["baryon_comoving"], s["baryon_max_physical"], a),
+            cur(s.get("nu_comoving", s["dm_comoving"]),
+                s.get("nu_max_physical", s["dm_max_physical"]), a),
+            float(s.get("background_fac", 0.0)))
+
+    def _grav_scalars(self) -> float:
+        """GT's cosmological scalars at ti_current (cosmology.c:243-295). Returns a."""
+        a = self.cosmology.scale_factor(self.ti_current)
+        self.GT.a = a
+        self.GT.a_factor_grav_accel = 1.0 / (a * a)
+        self.GT.time_step_factor = float(self.cosmology.H(a))
+        return a
+
+    def _kick_tables(self, kick: int) -> dict:
+        """cosmo.kick_tables_active at ti_current, built once per step and kick
+        for both sides."""
+        key = (self.ti_current, self.max_active_bin, kick)
+        if key not in self._tables:
+            if len(self._tables) >= 2:
+                self._tables.clear()
+            self._tables[key] = cosmo_mod.kick_tables_active(self.cosmology, self.ti_current, kick,
+                                                             self.max_active_bin)
+        return self._tables[key]
+
+    def _grav_interval(self, ti_lo: int, ti_hi: int) -> float:
+        """The gravity kick factor over [ti_lo, ti_hi]: the integral of dt / a
+        (kick_get_grav_kick_dt), or the physical time."""
+        if self.cosmology is None:
+            return (ti_hi - ti_lo) * self.time_base
+        return cosmo_mod._kick_integral(self.cosmology, ti_lo, ti_hi, 1.0)
+
+    def _drift_gparts(self, ti_old: int, ti_new: int) -> float:
+        """Drift the gspace; with a cosmology by the integral of dt / a^2, and
+        every gpart gets the softening at the new a in the same pass."""
+        dim = (self.box,) * 3
+        if self.cosmology is None:
+            dt = (ti_new - ti_old) * self.time_base
+            self.gs.drift(dt, self.periodic, dim)
+            return dt
+        cm = self.cosmology
+        dt = cosmo_mod._kick_integral(cm, ti_old, ti_new, 2.0) if ti_new > ti_old else 0.0
+        S = self._softening_params(cm.scale_factor(ti_new))
+        self.gs.drift(dt, self.periodic, dim, softening=S)
+        return dt
+
+    def _start_cosmology(self):
+        """init_step, after the upload: every gpart gets the softening at
+        a_begin (gravity_first_init_gpart) by a softened drift over nothing,
+        and the RMS constraint starts at FLT_MAX."""
+        self.dt_max_rms = float(np.finfo(np.float32).max)
+        self._rms_pending = False
+        self.GT.dt_max_RMS_displacement = self.dt_max_rms
+        self.T.dt_max_RMS_displacement = self.dt_max_rms  # (the gas's; NBody: GT again)
+        self._drift_gparts(0, 0)
+
+    # -- the RMS-displacement constraint ----------------------------------
+    def _rms_applies(self) -> bool:
+        """The reference recomputes the constraint only in a cosmological run
+        with a periodic mesh; elsewhere it stays FLT_MAX."""
+        return self.cosmology is not None and bool(self.mesh) and self.periodic
+
+    def _enqueue_rms(self):
+        if not self._rms_applies():
+            return
+        sp = getattr(self, "sp", None)
+        if sp is not None:
+            sp.displacement_sums_enqueue()
+        self.gs.displacement_sums_enqueue()
+        self._rms_pending = True
+
+    def _read_rms(self):
+        """The queued sums into e->dt_max_RMS_displacement (one host wait, on
+        mesh steps only), handed to the time-step parameters of both sides."""
+        if not self._rms_pending:
+            return
+        self._rms_pending = False
+        cm = self.cosmology
+        sp = getattr(self, "sp", None)
+        self.rms_sums = (sp.displacement_sums_result() if sp is not None else None,
+                         self.gs.displacement_sums_result())
+        R = abi.RmsParams(cm.Omega_cdm, cm.Omega_b, cm.H0, cm.scale_factor(self.ti_current),
+                          self.const_G, float(self.mesh["r_s"]), self.max_rms_displacement_factor)
+        self.dt_max_rms = float(lib.dt_max_rms_displacement(R, *self.rms_sums))
+        self.GT.dt_max_RMS_displacement = self.dt_max_rms
+        self.T.dt_max_RMS_displacement = self.dt_max_rms  # (the gas's; NBody: GT again)
 
     def _stats_params(self, extrapolate: int = 1) -> abi.StatsParams:
         """dt_kick_mesh_grav: from the middle of the mesh step that holds
@@ -244,11 +374,24 @@ class _GravityDriver:
         dt_mesh = 0.0
         if self.mesh and extrapolate and self.mesh_ti_end > 0:
             mid = (self.mesh_ti_beg + self.mesh_ti_end) // 2
-            dt_mesh = (self.ti_current - mid) * self.time_base
-        return abi.StatsParams(self.ti_current, self.time_base, extrapolate, self.periodic,
-                               (self.box,) * 3, 1.0, 1.0, dt_mesh)
+            if self.cosmology is None:
+                dt_mesh = (self.ti_current - mid) * self.time_base
+            elif mid != self.ti_current:
+                dt_mesh = (self._grav_interval(mid, self.ti_current) if mid < self.ti_current
+                           else -self._grav_interval(self.ti_current, mid))
+        cm = self.cosmology
+        if cm is None:
+            return abi.StatsParams(self.ti_current, self.time_base, extrapolate, self.periodic,
+                                   (self.box,) * 3, 1.0, 1.0, dt_mesh)
+        a = cm.scale_factor(self.ti_current)
+        S = abi.StatsParams(self.ti_current, self.time_base, extrapolate, self.periodic,
+                            (self.box,) * 3, 1.0 / a, a ** (-3.0 * (cosmo_mod.HYDRO_GAMMA - 1.0)),
+                            dt_mesh)
+        S.set_tables(**cosmo_mod.sync_tables(cm, self.ti_current))
+        return S
 
-    def _gkick_params(self, dt_mesh: float = 0.0) -> abi.GKickParams:
+    def _gkick_params(self, dt_mesh: float = 0.0, kick: int = 0) -> abi.GKickParams:
+        """kick (1 or 2): with a cosmology, which half-kick's table to hand on."""
         K = abi.GKickParams()
         K.ti_current = self.ti_current
         K.time_base = self.time_base
@@ -256,12 +399,17 @@ class _GravityDriver:
         K.dt_kick_mesh_grav = dt_mesh
         if dt_mesh != 0.0:
             self.mesh_kicks += 1
+        if self.cosmology is not None:
+            K.set_table(self._kick_tables(kick)["grav"])
         return K
 
     def _next_mesh_step(self) -> int:
-        """engine.c:3528-3550 without the RMS term: the length of the mesh
-        step that starts at ti_current."""
-        new_dti = int(self.GT.dt_max * self.GT.time_base_inv)
+        """engine.c:3528-3550: the length of the mesh step that starts at
+        ti_current, bounded by dt_max and by the RMS-displacement constraint
+        (FLT_MAX, so without effect, unless _read_rms computed it)."""
+        dt_mesh = float(np.float32(self.dt_max_rms)) * self.GT.time_step_factor
+        dt_mesh = min(dt_mesh, self.GT.dt_max)
+        new_dti = int(dt_mesh * self.GT.time_base_inv)
         line = MAX_NR_TIMESTEPS
         while new_dti < line:
             line //= 2
@@ -281,18 +429,19 @@ class _GravityDriver:
             return 0.0
         self.mesh_ti_beg = 0
         self.mesh_ti_end = self._next_mesh_step()
-        return (self.mesh_ti_end // 2) * self.time_base
+        return self._grav_interval(0, self.mesh_ti_end // 2)
 
     def _mesh_kicks_here(self):
         """(kick2's, kick1's) mesh half-kick at ti_current: half the mesh step
         that ends here and half the one that starts, (0, 0) elsewhere."""
         dt2 = dt1 = 0.0
         if self._mesh_step_ends():
-            dt2 = ((self.mesh_ti_end - self.mesh_ti_beg) // 2) * self.time_base
+            half = (self.mesh_ti_end - self.mesh_ti_beg) // 2
+            dt2 = self._grav_interval(self.ti_current - half, self.ti_current)
             new_dti = self._next_mesh_step()
             self.mesh_ti_beg = self.ti_current
             self.mesh_ti_end = self.ti_current + new_dti
-            dt1 = (new_dti // 2) * self.time_base
+            dt1 = self._grav_interval(self.ti_current, self.ti_current + new_dti // 2)
         return dt2, dt1
 
     def _set_potential_normalisation(self, g: np.ndarray, live: np.ndarray):
@@ -318,7 +467,7 @@ class _GravityDriver:
 
 class NBodyIntegrator(_GravityDriver):
     """A multi-step, multi-time-bin driver over one GravSpace: the gparts stay
-    on the device from the first upload on (non-cosmological).
+    on the device from the first upload on.
 
         init_step()      engine_init_particles: every live gpart active in bin
                          0, the tree build, gravity, the first time steps and
@@ -334,23 +483,39 @@ class NBodyIntegrator(_GravityDriver):
     G: abi.GravParams (its max_active_bin follows the run), T:
     abi.GTimestepParams (ti_current, max_active_bin and time_base_inv follow
     the run), mesh: None or dict(N=, r_s=): the periodic long-range force
-    (swh_gspace_pm_mesh) on the schedule of engine.c:3528-3550 without the
-    RMS-displacement term -- the mesh step is the largest step of the time
-    line <= dt_max, every gpart's step is <= dt_max too, so all gparts are
-    active where a mesh step ends; kick2 and kick1 there get half a mesh step
-    (runner_time_integration.c:128-138, 400-411), the others none.
+    (swh_gspace_pm_mesh) on the schedule of engine.c:3528-3550 -- the mesh
+    step is the largest step of the time line <= dt_max (and <= the
+    RMS-displacement constraint times H), every gpart's step is bounded by the
+    same two, so all gparts are active where a mesh step ends; kick2 and kick1
+    there get half a mesh step (runner_time_integration.c:128-138, 400-411),
+    the others none.
 
-    The step's one host wait is the record read, which delivers ti_end_min."""
+    cosmology: a cosmo.Cosmology; the time line then runs in log a (time_base
+    is the cosmology's, the argument is ignored) and softening= is required:
+    dict(dm_comoving=, dm_max_physical=, baryon_comoving=,
+    baryon_max_physical=[, background_fac=]), Plummer-equivalent lengths. The
+    drift is the integral of dt / a^2 and gives every gpart the softening of
+    gravity_props_update at the new a (swh_gspace_drift_softened); the kicks
+    are the integrals of dt / a per bin (cosmo.kick_tables_active) and over
+    the half mesh step; T carries a, a^-2 and H. With a periodic mesh the
+    RMS-displacement constraint (engine_recompute_displacement_constraint,
+    max_rms_displacement_factor) is recomputed from the device's sums after
+    the first mesh and wherever a mesh step ends, and bounds the gparts' steps
+    and the next mesh step until then. With cosmology=None nothing changes.
+
+    The step's one host wait is the record read, which delivers ti_end_min;
+    on a cosmological mesh step the read of the sums is one more."""
 
     def __init__(self, gspace, G: abi.GravParams, T: abi.GTimestepParams, time_base: float,
                  cdim: int, split_size: int = 64, max_depth: int = 12, box: float = 1.0,
-                 const_G: float = 1.0, mesh: dict = None):
-        if not time_base or time_base <= 0:
-            raise ValueError("time_base (time per tick) must be positive")
+                 const_G: float = 1.0, mesh: dict = None,
+                 cosmology: "cosmo_mod.Cosmology" = None, softening: dict = None,
+                 max_rms_displacement_factor: float = 0.25):
         self.gs = gspace
         self.G = G
         self.T = self.GT = T
-        self.time_base = float(time_base)
+        self.time_base = self._init_cosmology(cosmology, time_base, softening,
+                                              max_rms_displacement_factor)
         self.T.time_base_inv = 1.0 / self.time_base
         self.cdim, self.split_size, self.max_depth = int(cdim), int(split_size), int(max_depth)
         self.box = float(box)
@@ -367,6 +532,8 @@ class NBodyIntegrator(_GravityDriver):
         self.G.max_active_bin = self.max_active_bin
         self.T.max_active_bin = self.max_active_bin
         self.T.ti_current = self.ti_current
+        if self.cosmology is not None:
+            self._grav_scalars()
 
     _kick_params = _GravityDriver._gkick_params
 
@@ -389,13 +556,17 @@ class NBodyIntegrator(_GravityDriver):
         self._update_scalars()
         self._set_potential_normalisation(g, live)
         self.gs.upload(g)
+        if self.cosmology is not None:
+            self._start_cosmology()
         self._build()
         self.gravity()
+        self._enqueue_rms()
         self.statistics = []
         if statistics:
             self.collect_statistics(extrapolate=0)
+        self._read_rms()
         self.gs.timestep(self.T)
-        self.gs.kick1(self._kick_params(self._first_mesh_kick()))
+        self.gs.kick1(self._kick_params(self._first_mesh_kick(), 1))
         self.result = self.gs.step_result()
         return self.result
 
@@ -407,16 +578,18 @@ class NBodyIntegrator(_GravityDriver):
             raise RuntimeError(f"time line exhausted or stalled at {ti_old} -> {self.ti_current}")
         self.max_active_bin = get_max_active_bin(self.ti_current)
         self._update_scalars()
-        dt = (self.ti_current - ti_old) * self.time_base
-        self.gs.drift(dt, self.periodic, (self.box,) * 3)
+        dt = self._drift_gparts(ti_old, self.ti_current)
+        if self._mesh_step_ends():
+            self._enqueue_rms()
         if statistics:
             self.collect_statistics()
         self._build()
         return dt
 
     def end_step(self) -> dict:
+        self._read_rms()
         dt2, dt1 = self._mesh_kicks_here()
-        self.gs.end_step(self._kick_params(dt2), self.T, self._kick_params(dt1))
+        self.gs.end_step(self._kick_params(dt2, 2), self.T, self._kick_params(dt1, 1))
         self.result = self.gs.step_result()
         return self.result
 
@@ -432,9 +605,9 @@ class NBodyIntegrator(_GravityDriver):
 
 class CoupledIntegrator(_GravityDriver):
     """Self-gravitating gas: one HydroSpace and one GravSpace stepped together
-    (non-cosmological), the gas linked to its gas gparts on the device
-    (swh_space_link_gspace). Nothing leaves the device after init_step's
-    uploads: the gas reads its gravity from the linked records
+    (in physical time, or with cosmology= in log a), the gas linked to its gas
+    gparts on the device (swh_space_link_gspace). Nothing leaves the device
+    after init_step's uploads: the gas reads its gravity from the linked records
     (pull_gravity) and writes x, v_full and time_bin back into them
     (push_gparts), as SWIFT's part loops do through p->gpart.
 
@@ -458,20 +631,30 @@ class CoupledIntegrator(_GravityDriver):
     the gravity side's abi.GravParams / abi.GTimestepParams. Both sides share
     dt_max: the mesh step (NBodyIntegrator's schedule) must bound every
     particle's step. The two record reads are the step's only host waits
-    beyond those the hydro chain already has."""
+    beyond those the hydro chain already has.
+
+    cosmology, softening, max_rms_displacement_factor: as NBodyIntegrator's.
+    The gas side then gets Integrator's cosmological scalars and drift
+    factors, both sides the per-bin kick tables of cosmo.kick_tables_active
+    (kick2's and kick1's own), the limiter cosmo.limiter_tables, and
+    T.grav_dt_factor = 2 (1 / 3) a eta epsilon_baryon_cur follows the run. On a
+    mesh step the sums of both sides are queued after the drift and read
+    before the end of step: one more host wait, on mesh steps only. With
+    cosmology=None nothing changes."""
 
     def __init__(self, space, gspace, P: abi.HydroParams, T: abi.TimestepParams,
                  G: abi.GravParams, GT: abi.GTimestepParams, time_base: float, cdim: int,
                  split_size: int = 64, max_depth: int = 12, box: float = 1.0,
                  const_G: float = 1.0, min_u: float = 0.0, max_rel_dx: float = 0.1,
-                 mesh: dict = None, limiter: bool = False):
-        if not time_base or time_base <= 0:
-            raise ValueError("time_base (time per tick) must be positive")
+                 mesh: dict = None, limiter: bool = False,
+                 cosmology: "cosmo_mod.Cosmology" = None, softening: dict = None,
+                 max_rms_displacement_factor: float = 0.25):
         if T.dt_max != GT.dt_max:
             raise ValueError(f"the gas and the gparts need one dt_max: {T.dt_max} != {GT.dt_max}")
         self.sp, self.gs = space, gspace
         self.P, self.T, self.G, self.GT = P, T, G, GT
-        self.time_base = float(time_base)
+        self.time_base = self._init_cosmology(cosmology, time_base, softening,
+                                              max_rms_displacement_factor)
         self.P.time_base = self.time_base
         self.T.time_base_inv = self.GT.time_base_inv = 1.0 / self.time_base
         self.cdim, self.split_size, self.max_depth = int(cdim), int(split_size), int(max_depth)
@@ -499,14 +682,33 @@ class CoupledIntegrator(_GravityDriver):
         self.G.max_active_bin = self.max_active_bin
         self.GT.max_active_bin = self.max_active_bin
         self.GT.ti_current = self.ti_current
+        if self.cosmology is None:
+            return
+        _cosmo_gas_scalars(self.cosmology, self.ti_current, self.P, self.T)
+        a = self._grav_scalars()
+        # gravity_compute_timestep_self for the gas: 2 (1 / 3) a eta epsilon,
+        # epsilon the baryons' current (internal) softening
+        eps = float(self._softening_params(a).epsilon_baryon_cur)
+        self.T.grav_dt_factor = 2.0 * (1.0 / 3.0) * a * float(self.GT.eta) * eps
 
-    def _kick_params(self) -> abi.KickParams:
+    def _kick_params(self, kick: int = 0) -> abi.KickParams:
+        """kick (1 or 2): with a cosmology, which half-kick's tables to hand on."""
         K = abi.KickParams()
         K.ti_current = self.ti_current
         K.time_base = self.time_base
         K.max_active_bin = self.max_active_bin
         K.min_u = self.min_u
+        if self.cosmology is not None:
+            K.set_tables(**self._kick_tables(kick))
         return K
+
+    def _limiter_params(self) -> abi.LimiterParams:
+        L = abi.LimiterParams()
+        L.ti_current, L.time_base = self.ti_current, self.time_base
+        L.max_active_bin, L.min_u = self.max_active_bin, self.min_u
+        if self.cosmology is not None:
+            L.set_tables(*cosmo_mod.limiter_tables(self.cosmology, self.ti_current))
+        return L
 
     @staticmethod
     def merge_records(gas: dict, gparts: dict) -> dict:
@@ -559,15 +761,19 @@ class CoupledIntegrator(_GravityDriver):
         self.sp.upload(p)
         self.sp.upload_xparts(xparts)
         self.gs.upload(g)
+        if self.cosmology is not None:
+            self._start_cosmology()
         self.n_linked = self.sp.link(self.gs)
         self.sp.rebuild(self.P)
         self._build()
         self.gravity()
+        self._enqueue_rms()
         self.sp.pull_gravity()
         self.chain = self.sp.hydro_step(self.P)
         self.statistics = []
         if statistics:
             self.collect_statistics(extrapolate=0)
+        self._read_rms()
         self.sp.timestep_linked(self.T, self.P)
         self.gs.timestep(self.GT)
         self._push(time_bin=True)
@@ -578,8 +784,8 @@ class CoupledIntegrator(_GravityDriver):
     def kick1(self, dt_mesh: float):
         """Both first half-kicks and the push of v_full."""
         self.gas_mesh_kicks += 1 if dt_mesh != 0.0 else 0
-        self.sp.kick1_linked(self._kick_params(), self.P, dt_mesh)
-        self.gs.kick1(self._gkick_params(dt_mesh))
+        self.sp.kick1_linked(self._kick_params(1), self.P, dt_mesh)
+        self.gs.kick1(self._gkick_params(dt_mesh, 1))
         self._push(v_full=True)
 
     def drift_to_next(self, statistics: bool = False):
@@ -592,8 +798,7 @@ class CoupledIntegrator(_GravityDriver):
             raise RuntimeError(f"time line exhausted or stalled at {ti_old} -> {self.ti_current}")
         self.max_active_bin = get_max_active_bin(self.ti_current)
         self._update_scalars()
-        dt = (self.ti_current - ti_old) * self.time_base
-        Dp = abi.DriftParams(dt, dt, dt, dt, self.min_u)
+        Dp = _gas_drift_params(self.cosmology, ti_old, self.ti_current, self.time_base, self.min_u)
         self.sp.drift(Dp, self.P)
         if statistics:  # before the rebuild voids the pulled accelerations
             self.sp.statistics_enqueue(self._stats_params())
@@ -601,7 +806,9 @@ class CoupledIntegrator(_GravityDriver):
         if info["dx_max"] > self.max_rel_dx * min(info["cell_width"]):
             self.sp.rebuild(self.P)
             self.rebuilds += 1
-        self.gs.drift(dt, self.periodic, (self.box,) * 3)
+        dt = self._drift_gparts(ti_old, self.ti_current)
+        if self._mesh_step_ends():
+            self._enqueue_rms()
         if statistics:
             self.gs.statistics_enqueue(self._stats_params())
             self._read_statistics()
@@ -618,23 +825,24 @@ class CoupledIntegrator(_GravityDriver):
         return self.chain
 
     def end_step(self) -> dict:
+        self._read_rms()
         dt2, dt1 = self._mesh_kicks_here()
         self.gas_mesh_kicks += (dt2 != 0.0) + (dt1 != 0.0)
-        K = self._kick_params()
+        # one object serves both kicks without a cosmology; with one, kick2
+        # and kick1 integrate over different halves
+        K2 = self._kick_params(2)
+        K1 = K2 if self.cosmology is None else self._kick_params(1)
         if not self.limiter:
-            self.sp.end_step_linked(K, self.T, K, self.P, dt2, dt1)
-            self.gs.end_step(self._gkick_params(dt2), self.GT, self._gkick_params(dt1))
+            self.sp.end_step_linked(K2, self.T, K1, self.P, dt2, dt1)
+            self.gs.end_step(self._gkick_params(dt2, 2), self.GT, self._gkick_params(dt1, 1))
             self._push(v_full=True, time_bin=True)
             return self._read_records()
         # (init_step needs no limiter: everybody starts in bin 0.) The gspace
         # neither kicks nor time-steps gas gparts and its record does not
         # count them: the space's merged record is the whole merge, and the
         # push hands the woken particles' bins and v_full to their gparts
-        L = abi.LimiterParams()
-        L.ti_current, L.time_base = self.ti_current, self.time_base
-        L.max_active_bin, L.min_u = self.max_active_bin, self.min_u
-        self.sp.end_step_limited_linked(K, self.T, K, L, self.P, dt2, dt1)
-        self.gs.end_step(self._gkick_params(dt2), self.GT, self._gkick_params(dt1))
+        self.sp.end_step_limited_linked(K2, self.T, K1, self._limiter_params(), self.P, dt2, dt1)
+        self.gs.end_step(self._gkick_params(dt2, 2), self.GT, self._gkick_params(dt1, 1))
         self._push(v_full=True, time_bin=True)
         self._read_records()
         r = self.sp.limiter_result()

@@ -70,6 +70,10 @@ HIP_SYMBOLS = [
     "swh_gspace_statistics", "swh_gspace_statistics_result", "swh_gspace_sync_velocities",
     "swh_space_statistics_times", "swh_gspace_statistics_times",
     "swh_statistics_add", "swh_statistics_finalize",
+    "swh_gspace_drift_softened",
+    "swh_space_displacement_sums", "swh_space_displacement_sums_result",
+    "swh_gspace_displacement_sums", "swh_gspace_displacement_sums_result",
+    "swh_dt_max_rms_displacement",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -242,6 +246,14 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
         "swh_gspace_statistics_times": (C.c_int, [vp, P(C.c_float)]),
         "swh_statistics_add": (None, [P(abi.Statistics), P(abi.Statistics)]),
         "swh_statistics_finalize": (None, [P(abi.Statistics)]),
+        "swh_gspace_drift_softened": (C.c_int, [vp, P(abi.GDriftParams),
+                                                P(abi.GSofteningParams)]),
+        "swh_space_displacement_sums": (C.c_int, [vp]),
+        "swh_space_displacement_sums_result": (C.c_int, [vp, P(abi.DisplacementSums)]),
+        "swh_gspace_displacement_sums": (C.c_int, [vp]),
+        "swh_gspace_displacement_sums_result": (C.c_int, [vp, P(abi.DisplacementSums)]),
+        "swh_dt_max_rms_displacement": (C.c_float, [P(abi.RmsParams), P(abi.DisplacementSums),
+                                                    P(abi.DisplacementSums)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -314,6 +326,17 @@ def _check(status: int, where: str, lib: C.CDLL | None = None) -> None:
     if status != 0:
         detail = ((lib or load()).swh_last_error() or b"").decode(errors="replace")
         raise SwhError(status, where, detail)
+
+
+def dt_max_rms_displacement(R: abi.RmsParams, gas: abi.DisplacementSums = None,
+                            dm: abi.DisplacementSums = None) -> np.float32:
+    """e->dt_max_RMS_displacement of a cosmological run from the two species'
+    sums (engine_recompute_displacement_constraint, in float). A species that
+    is None or counted nothing gives FLT_MAX for its term. Host only."""
+    L = load()
+    return np.float32(L.swh_dt_max_rms_displacement(
+        C.byref(R), C.byref(gas) if gas is not None else None,
+        C.byref(dm) if dm is not None else None))
 
 
 def finalize_statistics(*parts: dict) -> dict:
@@ -593,6 +616,18 @@ class HydroSpace:
 
     def drift(self, D: abi.DriftParams, P: abi.HydroParams):
         _check(self._lib.swh_space_drift(self.handle, C.byref(D), C.byref(P)), "drift", self._lib)
+
+    def displacement_sums_enqueue(self):
+        """The sums of the RMS-displacement constraint over the owned live
+        particles (the drifted v, the mass) on the space's stream; no host wait."""
+        _check(self._lib.swh_space_displacement_sums(self.handle), "displacement_sums", self._lib)
+
+    def displacement_sums_result(self) -> abi.DisplacementSums:
+        """Wait for the last displacement_sums_enqueue."""
+        r = abi.DisplacementSums()
+        _check(self._lib.swh_space_displacement_sums_result(self.handle, C.byref(r)),
+               "displacement_sums_result", self._lib)
+        return r
 
     def set_owned(self, n_owned: int):
         """Caller indices >= n_owned become read-only halo (foreign) particles."""
@@ -878,11 +913,32 @@ class GravSpace:
         _check(self._lib.swh_gspace_set_step_layout(self.handle, C.byref(SL)), "set_step_layout",
                self._lib)
 
-    def drift(self, dt_drift: float, periodic: bool = False, dim=(1.0, 1.0, 1.0)):
+    def drift(self, dt_drift: float, periodic: bool = False, dim=(1.0, 1.0, 1.0),
+              softening: abi.GSofteningParams = None):
         """drift_gpart on every live gpart (+ the box wrap when periodic). The
-        installed tree is stale afterwards: build_tree or set_tree before tree()."""
+        installed tree is stale afterwards: build_tree or set_tree before tree().
+        softening: in the same pass every live gpart also gets the softening of
+        its type (gravity_predict_extra); dt_drift = 0 then leaves x as it is."""
         D = abi.GDriftParams(dt_drift, periodic, dim)
-        _check(self._lib.swh_gspace_drift(self.handle, C.byref(D)), "gspace_drift", self._lib)
+        if softening is None:
+            _check(self._lib.swh_gspace_drift(self.handle, C.byref(D)), "gspace_drift", self._lib)
+        else:
+            _check(self._lib.swh_gspace_drift_softened(self.handle, C.byref(D),
+                                                       C.byref(softening)),
+                   "gspace_drift_softened", self._lib)
+
+    def displacement_sums_enqueue(self):
+        """The sums of the RMS-displacement constraint over the live dark-matter
+        gparts (v_full, mass) on the gspace's stream; no host wait."""
+        _check(self._lib.swh_gspace_displacement_sums(self.handle), "gspace_displacement_sums",
+               self._lib)
+
+    def displacement_sums_result(self) -> abi.DisplacementSums:
+        """Wait for the last displacement_sums_enqueue."""
+        r = abi.DisplacementSums()
+        _check(self._lib.swh_gspace_displacement_sums_result(self.handle, C.byref(r)),
+               "gspace_displacement_sums_result", self._lib)
+        return r
 
     def init_grav(self, max_active_bin: int = abi.NUM_TIME_BINS):
         """gravity_init_gpart on the active gparts' records."""
