@@ -1202,6 +1202,68 @@ SWH_API float swh_dt_max_rms_displacement(const swh_rms_params *R,
                                           const swh_displacement_sums *gas,
                                           const swh_displacement_sums *dm);
 
+/* ------------------------------------------------------------------ */
+/* Friends-of-friends groups of a gspace (added to ABI v15; purely     */
+/* additive): SWIFT's fof_search_tree (src/fof.c) over the installed   */
+/* cell tree, on the device. Two gparts are linked iff the float r2 of */
+/* their separation (per axis in double, nearest image when periodic,  */
+/* rounded to float; r2 = dx*dx + dy*dy + dz*dz in float, no FMA) is   */
+/* strictly below l_x2; the groups are the connected components.       */
+/* Inhibited and not-yet-created gparts and neutrinos (type 6) link to */
+/* nobody, belong to no group and are counted nowhere. Nothing here    */
+/* writes a record, the tree, a multipole or marks the tree stale.     */
+/* ------------------------------------------------------------------ */
+typedef struct swh_fof_params {
+  double l_x2;              /* square of the linking length, > 0 and finite */
+  int32_t periodic;         /* nearest image in dim[] (then l_x < dim / 2 on every axis) */
+  int32_t min_group_size;   /* >= 1: smaller groups get no id and no catalogue entry */
+  double dim[3];
+  int64_t group_id_offset;  /* the largest group's id (fof.c: 1) */
+  int64_t group_id_default; /* the id of a gpart in no kept group (fof_props_default_group_id) */
+} swh_fof_params;
+typedef struct swh_fof_result {
+  int64_t n_linkable;     /* gparts that took part */
+  int64_t n_groups;       /* groups of at least min_group_size */
+  int64_t n_in_groups;    /* their members */
+  int64_t max_group_size;
+  int64_t n_leaf_pairs;   /* (leaf, leaf) entries searched, a leaf with itself included */
+  int64_t n_pair_tests;   /* unordered gpart pairs tested */
+  int64_t n_links;        /* of those, pairs found linked */
+} swh_fof_result;
+/* The search on the gspace's stream over the installed tree (built or set):
+ * the leaf pairs whose gparts' boxes lie within l_x, the links and a lock-free
+ * union-find whose roots are the groups' smallest member indices, then the
+ * catalogue: the groups of at least min_group_size ranked by size descending,
+ * ties by root ascending, group k with id group_id_offset + k, its mass (sum of
+ * the masses in double) and centre of mass (sum of m x nearest(x - x_root) over
+ * the mass, plus x_root, box-wrapped when periodic). No floating-point
+ * atomics: the same state gives the same bits on every call, and the partition
+ * depends on no tree. The host reads a few counts per tree level and the
+ * number of groups; no gpart leaves the device. Indices are in the current
+ * device order (swh_gspace_tree_order maps them to the upload).
+ * SWH_ERR_STATE before swh_gspace_upload, without a tree, or with a tree made
+ * stale by swh_gspace_drift; SWH_ERR_ARG for l_x2 <= 0 or not finite,
+ * min_group_size < 1, a periodic l_x >= dim / 2, or more than 32768 top-level
+ * cells. An empty set gives zero counts. The type is read through
+ * swh_gspace_set_step_layout; without it no gpart is a neutrino. */
+SWH_API swh_status swh_gspace_fof(swh_gspace *g, const swh_fof_params *F);
+/* Waits for the last swh_gspace_fof; SWH_ERR_STATE if there was none (so the
+ * four calls below). */
+SWH_API swh_status swh_gspace_fof_result(swh_gspace *g, swh_fof_result *out);
+/* n entries: the root of every gpart's group (a singleton is its own), -1 for
+ * a gpart left out. */
+SWH_API swh_status swh_gspace_fof_roots(swh_gspace *g, int32_t *roots);
+/* n entries: group_id_offset + rank, or group_id_default. */
+SWH_API swh_status swh_gspace_fof_group_ids(swh_gspace *g, int64_t *ids);
+/* The kept groups in rank order; com: 3 per group; any pointer may be NULL.
+ * SWH_ERR_ARG unless ngroups equals the result's n_groups. */
+SWH_API swh_status swh_gspace_fof_groups(swh_gspace *g, int64_t *size, double *mass, double *com,
+                                         int32_t *root, int32_t ngroups);
+/* Device time of the stages of the last swh_gspace_fof (ms, HIP events on the
+ * gspace's stream; waits for them): ms[0..4) = leaf pairs (with the host's
+ * reads of the level counts), links, flatten, catalogue. -1 before any call. */
+SWH_API swh_status swh_gspace_fof_times(swh_gspace *g, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

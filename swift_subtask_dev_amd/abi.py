@@ -501,6 +501,38 @@ class Statistics(C.Structure):
         return s
 
 
+FOF_DEFAULT_GROUP_ID = 2147483647  # src/fof.c fof_props_default_group_id
+FOF_DEFAULT_GROUP_ID_OFFSET = 1    # fof_props_default_group_id_offset
+TYPE_NEUTRINO = 6                  # swift_type_neutrino
+
+
+class FofParams(C.Structure):
+    """swh_fof_params: the friends-of-friends search of a gspace."""
+
+    _fields_ = [("l_x2", C.c_double), ("periodic", C.c_int32), ("min_group_size", C.c_int32),
+                ("dim", C.c_double * 3), ("group_id_offset", C.c_int64),
+                ("group_id_default", C.c_int64)]
+
+    def __init__(self, l_x2=0.0, periodic=0, min_group_size=20, dim=(1.0, 1.0, 1.0),
+                 group_id_offset=FOF_DEFAULT_GROUP_ID_OFFSET,
+                 group_id_default=FOF_DEFAULT_GROUP_ID):
+        super().__init__(float(l_x2), int(periodic), int(min_group_size),
+                         (C.c_double * 3)(*dim), int(group_id_offset), int(group_id_default))
+
+
+FOF_RESULT_FIELDS = ("n_linkable", "n_groups", "n_in_groups", "max_group_size", "n_leaf_pairs",
+                     "n_pair_tests", "n_links")
+
+
+class FofResult(C.Structure):
+    """swh_fof_result: the counts of the last search."""
+
+    _fields_ = [(n, C.c_int64) for n in FOF_RESULT_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in FOF_RESULT_FIELDS}
+
+
 class GCell(C.Structure):
     """swh_gcell: a tree cell's gpart range, progeny and geometry."""
 

@@ -290,3 +290,27 @@ def small_cosmo_volume_params(max_active_bin: int = SCV_FIRST_BIN) -> tuple:
                    Omega_lambda=ics.SCV_OMEGA_L, H0=ics.SCV_H0, a_begin=ics.SCV_A_BEGIN, a_end=1.0)
     P = cosmological_params(cm, SCV_TI_CURRENT, max_active_bin=max_active_bin)
     return cm, P
+
+
+def fof_linking_length(ratio: float, dm_mass: float, cosmo: Cosmology, with_hydro: bool,
+                       const_G: float = 1.0) -> float:
+    """The friends-of-friends linking length from the mean separation of the
+    dark-matter particles (fof_allocate, src/fof.c:296-314): ratio *
+    cbrt(dm_mass / rho_mean), rho_mean = Omega_cdm rho_crit,0 with gas present
+    and (Omega_cdm + Omega_b) rho_crit,0 without; rho_crit,0 = 3 H0^2 /
+    (8 pi G). dm_mass: the mass of the first existing dark-matter gpart
+    (fof.c:264-274; first_dm_mass)."""
+    rho_crit0 = 3.0 * cosmo.H0 * cosmo.H0 / (8.0 * math.pi * const_G)
+    omega = cosmo.Omega_cdm if with_hydro else cosmo.Omega_cdm + cosmo.Omega_b
+    if not (dm_mass > 0.0 and omega > 0.0 and ratio > 0.0):
+        raise ValueError("fof_linking_length needs ratio, dm_mass and the matter density > 0")
+    return float(ratio * np.cbrt(dm_mass / (omega * rho_crit0)))
+
+
+def first_dm_mass(gparts: np.ndarray) -> float:
+    """The mass of the first dark-matter gpart (type 1) that is neither
+    inhibited nor not yet created (fof.c:264-274); 0 when there is none."""
+    ok =((gparts["type"] == 1) & (gparts["time_bin"] != abi.TIME_BIN_INHIBITED)
+          & (gparts["time_bin"] != abi.TIME_BIN_NOT_CREATED))
+    k = np.flatnonzero(ok)
+    return float(gparts["mass"][k[0]]) if len(k) else 0.0

@@ -1369,6 +1369,7 @@ swh_status swh_gspace_destroy(swh_gspace* g) {
   gtree_release(g);
   gstep_release(g);
   couple_release(g);
+  fof_release(g);
   (void)hipStreamDestroy(g->stream);
   delete g;
   return SWH_OK;

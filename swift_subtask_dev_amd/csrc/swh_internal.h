@@ -202,6 +202,10 @@ struct RmsState {
   ~RmsState() { release(); }  // with its space (the destroy calls' delete)
 };
 
+// The friends-of-friends search of a gspace (swh_fof.hip): its scratch, its
+// outputs and the pinned copy of its counters.
+struct FofState;
+
 // Device copy of the AoS layout (offsets), passed by value to kernels.
 struct Layout {
   int stride;
@@ -472,9 +476,11 @@ struct swh_gspace {
   hipEvent_t link_event = nullptr;  // recorded on this gspace's stream for the space's
   swh::StatsState stats;  // swh_gspace_statistics / _sync_velocities (swh_stats.hip)
   swh::RmsState rms;      // swh_gspace_displacement_sums (swh_rms.hip)
+  swh::FofState* fof = nullptr;  // swh_gspace_fof (swh_fof.hip), made by the first call
 };
 
 namespace swh {
+void fof_release(swh_gspace* g);   // swh_fof.hip: the search's buffers, event and timer
 void mesh_release(swh_gspace* g);  // swh_mesh.hip: mesh buffers and hipFFT plans
 void gtree_release(swh_gspace* g);  // swh_gtree.hip: the tree build's scratch and events
 void gstep_release(swh_gspace* g);  // swh_gkick.hip: the step record and the stage timer

@@ -271,6 +271,9 @@ class _GravityDriver:
         self.statistics = []  # (ti_current, finalised statistics) of the collected steps
         self.dt_max_rms = float(np.finfo(np.float32).max)
         self._rms_pending = False
+        self.groups = None  # (ti_current, the result of the last find_groups)
+        self._tree_fresh = False  # the installed tree is of the gparts as they are
+        self._dm_mass = 0.0  # the first existing dark-matter gpart's (fof.c:264-274)
 
     # -- cosmological factors ---------------------------------------------
     def _softening_params(self, a: float) -> abi.GSofteningParams:
@@ -317,6 +320,7 @@ class _GravityDriver:
         """Drift the gspace; with a cosmology by the integral of dt / a^2, and
         every gpart gets the softening at the new a in the same pass."""
         dim = (self.box,) * 3
+        self._tree_fresh = False
         if self.cosmology is None:
             dt = (ti_new - ti_old) * self.time_base
             self.gs.drift(dt, self.periodic, dim)
@@ -453,6 +457,7 @@ class _GravityDriver:
 
     def _build(self):
         _, tops = self.gs.build_tree(self.cdim, self.split_size, self.box, self.max_depth)
+        self._tree_fresh = True
         if self.tops is None or not np.array_equal(tops, self.tops):
             self.tops = tops
             self._pairs = ics.top_level_pairs(tops)
@@ -463,6 +468,43 @@ class _GravityDriver:
             self.gs.pm_mesh(int(self.mesh["N"]), self.box, float(self.mesh["r_s"]), self.const_G)
         self.gs.tree(self.G, self.tops, self._pairs, stats=False)
         self.gs.end_force(self.const_G, self.potential_normalisation, self.periodic)
+
+    # -- friends-of-friends groups ----------------------------------------
+    def _fresh_tree(self):
+        """A tree of the gparts as they are: the driver's own build if a drift
+        left the installed one stale."""
+        if not self._tree_fresh:
+            self._build()
+
+    def find_groups(self, linking_length: float = None, linking_length_ratio: float = None,
+                    min_group_size: int = 20,
+                    group_id_offset: int = abi.FOF_DEFAULT_GROUP_ID_OFFSET,
+                    group_id_default: int = abi.FOF_DEFAULT_GROUP_ID,
+                    upload_order: bool = False) -> dict:
+        """The friends-of-friends groups of the gparts at ti_current (SWIFT's
+        --fof, engine_fof), on the device: valid wherever collect_statistics is,
+        after the drift. linking_length: absolute (FOF:absolute_linking_length);
+        or linking_length_ratio of the mean dark-matter separation
+        (cosmo.fof_linking_length; needs the cosmology). Nothing of the run is
+        changed: a run with find_groups equals one without bit for bit. Returns
+        GravSpace.fof's dict (plus linking_length) and keeps (ti_current, dict)
+        in .groups. Indices are in device order unless upload_order."""
+        if (linking_length is None) == (linking_length_ratio is None):
+            raise ValueError("give linking_length or linking_length_ratio")
+        if linking_length is None:
+            if self.cosmology is None:
+                raise ValueError("linking_length_ratio needs a cosmology "
+                                 "(the mean matter density)")
+            linking_length = cosmo_mod.fof_linking_length(
+                linking_length_ratio, self._dm_mass, self.cosmology,
+                with_hydro=hasattr(self, "sp"), const_G=self.const_G)
+        self._fresh_tree()
+        F = abi.FofParams(float(linking_length) ** 2, int(self.periodic), min_group_size,
+                          (self.box,) * 3, group_id_offset, group_id_default)
+        res = self.gs.fof(F, upload_order=upload_order)
+        res["linking_length"] = float(linking_length)
+        self.groups = (self.ti_current, res)
+        return res
 
 
 class NBodyIntegrator(_GravityDriver):
@@ -555,6 +597,7 @@ class NBodyIntegrator(_GravityDriver):
         self.mesh_kicks = 0
         self._update_scalars()
         self._set_potential_normalisation(g, live)
+        self._dm_mass = cosmo_mod.first_dm_mass(g)
         self.gs.upload(g)
         if self.cosmology is not None:
             self._start_cosmology()
@@ -730,6 +773,14 @@ class CoupledIntegrator(_GravityDriver):
     def _push(self, **what):
         self.sp.push_gparts(periodic=self.periodic, dim=(self.box,) * 3, **what)
 
+    def _fresh_tree(self):
+        """drift_to_next pushes the gas positions into the gas gparts before it
+        builds the tree, so a fresh tree has them; after a drift without that
+        build they are pushed here first."""
+        if not self._tree_fresh:
+            self._push(x=True)
+            self._build()
+
     # -- the entry points -----------------------------------------------------
     def collect_statistics(self, extrapolate: int = 1) -> dict:
         """Both sides queued, then both results: the gas sums from the space,
@@ -760,6 +811,7 @@ class CoupledIntegrator(_GravityDriver):
         self._set_potential_normalisation(g, g["time_bin"] != abi.TIME_BIN_INHIBITED)
         self.sp.upload(p)
         self.sp.upload_xparts(xparts)
+        self._dm_mass = cosmo_mod.first_dm_mass(g)
         self.gs.upload(g)
         if self.cosmology is not None:
             self._start_cosmology()

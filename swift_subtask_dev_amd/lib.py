@@ -74,6 +74,8 @@ HIP_SYMBOLS = [
     "swh_space_displacement_sums", "swh_space_displacement_sums_result",
     "swh_gspace_displacement_sums", "swh_gspace_displacement_sums_result",
     "swh_dt_max_rms_displacement",
+    "swh_gspace_fof", "swh_gspace_fof_result", "swh_gspace_fof_roots",
+    "swh_gspace_fof_group_ids", "swh_gspace_fof_groups", "swh_gspace_fof_times",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -254,7 +256,17 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
         "swh_gspace_displacement_sums_result": (C.c_int, [vp, P(abi.DisplacementSums)]),
         "swh_dt_max_rms_displacement": (C.c_float, [P(abi.RmsParams), P(abi.DisplacementSums),
                                                     P(abi.DisplacementSums)]),
+        "swh_gspace_fof": (C.c_int, [vp, P(abi.FofParams)]),
+        "swh_gspace_fof_result": (C.c_int, [vp, P(abi.FofResult)]),
+        "swh_gspace_fof_roots": (C.c_int, [vp, vp]),
+        "swh_gspace_fof_group_ids": (C.c_int, [vp, vp]),
+        "swh_gspace_fof_groups": (C.c_int, [vp, vp, vp, vp, vp, i32]),
+        "swh_gspace_fof_times": (C.c_int, [vp, P(C.c_float)]),
     }
+    missing = [name for name in sigs if not hasattr(lib, name)]
+    if missing:
+        raise ImportError(f"{path} lacks {', '.join(missing)}: rebuild it "
+                          "(`python -m swift_subtask_dev_amd.build`)")
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -1022,6 +1034,76 @@ class GravSpace:
         _check(self._lib.swh_gspace_statistics_times(self.handle, ms), "gspace_statistics_times",
                self._lib)
         return dict(zip(("statistics", "sync_velocities"), map(float, ms)))
+
+    # ---- friends-of-friends groups (swh_fof.hip) ---------------------------
+    def fof_enqueue(self, F: abi.FofParams):
+        """Queue the search over the installed tree on the gspace's stream."""
+        _check(self._lib.swh_gspace_fof(self.handle, C.byref(F)), "gspace_fof", self._lib)
+
+    def fof_result(self) -> dict:
+        """Wait for the last fof_enqueue; its counts."""
+        r = abi.FofResult()
+        _check(self._lib.swh_gspace_fof_result(self.handle, C.byref(r)), "gspace_fof_result",
+               self._lib)
+        return r.as_dict()
+
+    def fof_roots(self) -> np.ndarray:
+        """The root of every gpart's group in device order (-1: left out)."""
+        out = np.zeros(getattr(self, "_n", 0), dtype=np.int32)
+        _check(self._lib.swh_gspace_fof_roots(self.handle, _ptr(out)), "gspace_fof_roots",
+               self._lib)
+        return out
+
+    def fof_group_ids(self) -> np.ndarray:
+        out = np.zeros(getattr(self, "_n", 0), dtype=np.int64)
+        _check(self._lib.swh_gspace_fof_group_ids(self.handle, _ptr(out)), "gspace_fof_group_ids",
+               self._lib)
+        return out
+
+    def fof_groups(self, ngroups: int = None) -> dict:
+        """The kept groups in rank order: size, mass, com (n x 3), root."""
+        if ngroups is None:
+            ngroups = self.fof_result()["n_groups"]
+        out = {"size": np.zeros(ngroups, dtype=np.int64), "mass": np.zeros(ngroups),
+               "com": np.zeros((ngroups, 3)), "root": np.zeros(ngroups, dtype=np.int32)}
+        _check(self._lib.swh_gspace_fof_groups(self.handle, _ptr(out["size"]), _ptr(out["mass"]),
+                                               _ptr(out["com"]), _ptr(out["root"]), ngroups),
+               "gspace_fof_groups", self._lib)
+        return out
+
+    def fof(self, F: abi.FofParams, upload_order: bool = False) -> dict:
+        """The search and every output: the counts, `roots` and `group_ids`
+        per gpart, `groups` per kept group. Indices are in device order;
+        upload_order=True maps the per-gpart arrays back through tree_order
+        and names every group by its smallest index in the upload, so that
+        the roots do not depend on the tree (the ranks still break ties of
+        size by the root in device order)."""
+        self.fof_enqueue(F)
+        res = self.fof_result()
+        res["roots"] = self.fof_roots()
+        res["group_ids"] = self.fof_group_ids()
+        res["groups"] = self.fof_groups(res["n_groups"])
+        if upload_order and len(res["roots"]):
+            order = self.tree_order()
+            dev = res["roots"]
+            live = dev >= 0
+            # per device root: the smallest upload index among its members
+            first = np.full(len(dev), -1, dtype=np.int64)
+            first[dev[live]] = len(dev)
+            np.minimum.at(first, dev[live], order[live])
+            roots = np.full(len(dev), -1, dtype=np.int32)
+            roots[order[live]] = first[dev[live]]
+            ids = np.empty_like(res["group_ids"])
+            ids[order] = res["group_ids"]
+            res["roots"], res["group_ids"] = roots, ids
+            res["groups"]["root"] = first[res["groups"]["root"]].astype(np.int32)
+        return res
+
+    def fof_ms(self) -> dict:
+        """HIP-event times (ms) of the stages of the last search."""
+        ms = (C.c_float * 4)()
+        _check(self._lib.swh_gspace_fof_times(self.handle, ms), "gspace_fof_times", self._lib)
+        return dict(zip(("leaf_pairs", "links", "flatten", "catalogue"), map(float, ms)))
 
     def sync(self):
         _check(self._lib.swh_gspace_sync(self.handle), "gspace_sync", self._lib)
