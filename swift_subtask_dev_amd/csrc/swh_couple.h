@@ -21,6 +21,7 @@
 
 #include <stdint.h>
 
+#include "swh_grec.h"
 #include "swh_gstep.h"
 #include "swh_timeline.h"
 
@@ -36,15 +37,9 @@ namespace swh {
 constexpr uint32_t kPushX = 1u, kPushVFull = 2u, kPushTimeBin = 4u;
 constexpr int kGpartTypeGas = 0;  // swift_type_gas (src/part_type.h:28)
 
-// The offsets of a gpart record the link touches. id_or_neg_offset is the
-// first member of struct gpart in every gravity scheme of the reference.
-struct CoupleLayout {
-  int stride, id, x, v_full, a_grav, a_grav_mesh, time_bin, type;
-};
-
 // The part a record names: its caller index j when the record is a live gas
 // gpart (*gas) that names a part of [0, n); -1 otherwise.
-SWH_HD int64_t couple_decode(const CoupleLayout& L, const char* r, int64_t n, bool* gas) {
+SWH_HD int64_t couple_decode(const GRecLayout& L, const char* r, int64_t n, bool* gas) {
   const int bin = *reinterpret_cast<const int8_t*>(r + L.time_bin);
   const int type = *reinterpret_cast<const int8_t*>(r + L.type);
   *gas = bin != kGpartBinInhibited && type == kGpartTypeGas;
@@ -54,7 +49,7 @@ SWH_HD int64_t couple_decode(const CoupleLayout& L, const char* r, int64_t n, bo
 }
 
 // pull: the record's a_grav and a_grav_mesh
-SWH_HD void couple_pull(const CoupleLayout& L, const char* r, float a_grav[3],
+SWH_HD void couple_pull(const GRecLayout& L, const char* r, float a_grav[3],
                         float a_grav_mesh[3]) {
   const float* a = reinterpret_cast<const float*>(r + L.a_grav);
   const float* m = reinterpret_cast<const float*>(r + L.a_grav_mesh);
@@ -66,7 +61,7 @@ SWH_HD void couple_pull(const CoupleLayout& L, const char* r, float a_grav[3],
 
 // push: the part's values into the record; x wrapped with drift_gpart's
 // expression when periodic. Every other byte of the record stays.
-SWH_HD void couple_push(const CoupleLayout& L, char* r, uint32_t what, const double x[3],
+SWH_HD void couple_push(const GRecLayout& L, char* r, uint32_t what, const double x[3],
                         const float v_full[3], int time_bin, int periodic,
                         const double dim[3]) {
   if (what & kPushX) {

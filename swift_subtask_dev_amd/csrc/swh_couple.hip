@@ -27,7 +27,7 @@ enum { LC_LINKED = 0, LC_RANGE, LC_DUP, LC_INHIBITED, LC_SLOTS };
 
 // Per record: a live gas gpart must name a part of [0, n) that no other names.
 // mark[j] counts the records that name part j (a vector atomic add).
-__global__ __launch_bounds__(256) void link_mark_kernel(CoupleLayout L,
+__global__ __launch_bounds__(256) void link_mark_kernel(GRecLayout L,
                                                         const char* __restrict__ aos, int64_t ng,
                                                         int64_t n, int* __restrict__ mark,
                                                         unsigned int* __restrict__ cnt) {
@@ -78,7 +78,7 @@ __global__ void link_flags_kernel(const int* __restrict__ perm, const int* __res
   if (hasg_s) hasg_s[i] = mark[perm[i]] > 0 ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void pull_kernel(CoupleLayout L, const char* __restrict__ aos,
+__global__ __launch_bounds__(256) void pull_kernel(GRecLayout L, const char* __restrict__ aos,
                                                    int64_t ng, int64_t n,
                                                    const int* __restrict__ iperm,
                                                    float4* __restrict__ gp_agrav,
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void pull_kernel(CoupleLayout L, const char* _
   }
 }
 
-__global__ __launch_bounds__(256) void push_kernel(CoupleLayout L, char* __restrict__ aos,
+__global__ __launch_bounds__(256) void push_kernel(GRecLayout L, char* __restrict__ aos,
                                                    int64_t ng, int64_t n,
                                                    const int* __restrict__ iperm,
                                                    const PosRec* __restrict__ pos,
@@ -127,19 +127,14 @@ __global__ __launch_bounds__(256) void push_kernel(CoupleLayout L, char* __restr
   }
 }
 
-// Every offset the kernels use, compared with the stride.
-static swh_status couple_layout(const swh_gspace* g, CoupleLayout* out) {
-  const GLayout& G = g->layout;
-  const swh_gpart_step_layout& S = g->step_layout;
-  CoupleLayout L{G.stride, 0, G.x, S.off_v_full, G.a_grav, S.off_a_grav_mesh, G.time_bin,
-                 S.off_type};
-  if (L.stride < 8 || L.stride % 8 != 0 || L.x < 8 || L.x % 8 != 0 || L.x + 24 > L.stride ||
-      !float_field_ok(L.v_full, 3, L.stride) || !float_field_ok(L.a_grav, 3, L.stride) ||
-      !float_field_ok(L.a_grav_mesh, 3, L.stride) || L.time_bin < 8 || L.time_bin >= L.stride ||
-      L.type < 8 || L.type >= L.stride) {
-    set_error("the link needs id_or_neg_offset at byte 0 and x, v_full, a_grav, a_grav_mesh, "
-              "time_bin and type inside the gpart record of %d bytes, aligned to their type",
-              L.stride);
+// The record as the link's kernels see it: the fields they touch inside the
+// stride and clear of id_or_neg_offset, which owns bytes 0..8.
+static swh_status link_record(const swh_gspace* g, GRecLayout* out) {
+  const GRecLayout L = grec_layout(g);
+  SWH_TRY(grec_require(L, kNeedLink, "the gas link"));
+  if (L.x < 8 || L.time_bin < 8 || L.type < 8) {
+    set_error("the link needs id_or_neg_offset at byte 0: x %d, time_bin %d and type %d must lie "
+              "behind it", L.x, L.time_bin, L.type);
     return SWH_ERR_ARG;
   }
   *out = L;
@@ -240,8 +235,8 @@ swh_status swh_space_link_gspace(swh_space* s, swh_gspace* g, int64_t* n_linked)
               "swh_gspace_set_step_layout first");
     return SWH_ERR_ARG;
   }
-  CoupleLayout L{};
-  if (g->n > 0) SWH_TRY(couple_layout(g, &L));
+  GRecLayout L{};
+  if (g->n > 0) SWH_TRY(link_record(g, &L));
   SWH_HIP(hipSetDevice(s->ctx->device));
   hipStream_t st = s->stream;
   unsigned int h[LC_SLOTS] = {0, 0, 0, 0};
@@ -304,8 +299,8 @@ swh_status swh_space_pull_gravity(swh_space* s) {
     s->gp_pulled = true;
     return SWH_OK;
   }
-  CoupleLayout L;
-  SWH_TRY(couple_layout(g, &L));
+  GRecLayout L;
+  SWH_TRY(link_record(g, &L));
   SWH_HIP(hipSetDevice(s->ctx->device));
   SWH_TRY(order_streams(&g->link_event, g->stream, s->stream));
   SWH_TRY(s->link_timer.begin(LT_PULL, s->stream));
@@ -334,8 +329,8 @@ swh_status swh_space_push_gparts(swh_space* s, const swh_push_params* Q) {
   SWH_TRY(linked(s, "swh_space_push_gparts"));
   swh_gspace* g = s->link;
   if (s->n_linked == 0 || Q->what == 0) return SWH_OK;
-  CoupleLayout L;
-  SWH_TRY(couple_layout(g, &L));
+  GRecLayout L;
+  SWH_TRY(link_record(g, &L));
   SWH_HIP(hipSetDevice(s->ctx->device));
   if (Q->what & SWH_PUSH_V_FULL) SWH_TRY(space_ensure_xsorted(s));
   SWH_TRY(order_streams(&s->link_event, s->stream, g->stream));

@@ -37,6 +37,7 @@
 
 #include "swh_internal.h"
 #include "swh_fof.h"
+#include "swh_grec.h"
 #include "swh_wave.h"
 
 // a * b + c stays two roundings, in every instantiation alike
@@ -96,12 +97,6 @@ void fof_release(swh_gspace* g) {
   g->fof = nullptr;
 }
 
-// every offset of a gpart record the search reads (type < 0: no type field is
-// known, no gpart is a neutrino)
-struct FofLayout {
-  int stride, x, mass, time_bin, type;
-};
-
 struct FofDev {
   double l_x2;
   double dim[3];
@@ -112,7 +107,8 @@ __device__ __forceinline__ void ctr_add(unsigned long long* c, unsigned long lon
   if (v) atomicAdd(c, v);
 }
 
-__global__ __launch_bounds__(256) void fof_prep_kernel(FofLayout L, const char* __restrict__ aos,
+// (without a step layout no type field is known: no gpart is a neutrino)
+__global__ __launch_bounds__(256) void fof_prep_kernel(GRecLayout L, const char* __restrict__ aos,
                                                        int n, double4* __restrict__ xm,
                                                        int* __restrict__ parent,
                                                        unsigned long long* __restrict__ ctr) {
@@ -120,11 +116,12 @@ __global__ __launch_bounds__(256) void fof_prep_kernel(FofLayout L, const char* 
   bool ok = false;
   if (i < n) {
     const char* r = aos + (size_t)i * L.stride;
-    const double* x = reinterpret_cast<const double*>(r + L.x);
-    const int bin = *reinterpret_cast<const int8_t*>(r + L.time_bin);
-    const int type = L.type >= 0 ? (int)*reinterpret_cast<const int8_t*>(r + L.type) : 0;
-    ok = fof_linkable(bin, type);
-    xm[i] = make_double4(x[0], x[1], x[2], (double)*reinterpret_cast<const float*>(r + L.mass));
+    GRec<false> g;
+    g.load<kNeedFof>(L, r);
+    g.type = 0;
+    if (L.type >= 0) g.load<GF_TYPE>(L, r);
+    ok = fof_linkable(g.bin, g.type);
+    xm[i] = make_double4(g.x[0], g.x[1], g.x[2], (double)g.mass);
     parent[i] = ok ? i : -1;
   }
   const unsigned long long m = __ballot(ok);
@@ -516,23 +513,6 @@ static swh_status fof_read_counters(FofState& F, int count, hipStream_t st) {
   return SWH_OK;
 }
 
-static swh_status fof_layout(const swh_gspace* g, FofLayout* out) {
-  const GLayout& G = g->layout;
-  FofLayout L{G.stride, G.x, G.mass, G.time_bin,
-              g->step_layout_set ? g->step_layout.off_type : -1};
-  // (x is read as doubles: its offset and the stride keep every record's 8-byte aligned)
-  if (L.stride <= 0 || L.stride % 8 != 0 || L.x < 0 || L.x % 8 != 0 || L.x + 24 > L.stride ||
-      !float_field_ok(L.mass, 1, L.stride) || L.time_bin < 0 || L.time_bin >= L.stride ||
-      L.type >= L.stride) {
-    set_error("swh_gspace_fof: x, mass, time_bin and type must lie inside the gpart record of %d "
-              "bytes, aligned to their type", L.stride);
-    return SWH_ERR_ARG;
-  }
-  if (L.type < 0) L.type = -1;
-  *out = L;
-  return SWH_OK;
-}
-
 static swh_status fof_params(const swh_fof_params* F, FofDev* d) {
   if (!(F->l_x2 > 0.) || !std::isfinite(F->l_x2)) {
     set_error("swh_gspace_fof: l_x2 = %g must be positive and finite", F->l_x2);
@@ -691,8 +671,8 @@ swh_status swh_gspace_fof(swh_gspace* g, const swh_fof_params* Fp) {
               (int)g->tree_tops.size(), kFofMaxTops);
     return SWH_ERR_ARG;
   }
-  FofLayout L{};
-  SWH_TRY(fof_layout(g, &L));
+  const GRecLayout L = grec_layout(g);
+  SWH_TRY(grec_require(L, kNeedFof | (g->step_layout_set ? GF_TYPE : 0u), "swh_gspace_fof"));
   F.has = false;
   const int n = (int)g->n;
   const size_t N = (size_t)n;

@@ -1390,7 +1390,6 @@ swh_status swh_gspace_upload(swh_gspace* g, const void* gparts, int64_t count,
   g->uploaded = true;
   g->order_valid = false;  // swh_gspace_tree_order: the records are in upload order
   g->tree_stale = false;   // a drift's staleness went with the records it moved
-  g->step_checked = false;
   g->gstep.invalidate();
   if (count == 0) return SWH_OK;
   SWH_TRY(g->aos.reserve((size_t)count * L.stride));

@@ -224,10 +224,6 @@ struct GLayout {
   int old_a_grav_norm;  // -1: not in the record (the adaptive MAC then sees 0)
 };
 swh_status make_glayout(const swh_gpart_layout* L, GLayout* out);
-// `count` floats at byte `off` of a record lie inside its stride, 4-byte aligned
-inline bool float_field_ok(int off, int count, int stride) {
-  return off >= 0 && off % 4 == 0 && off + 4 * count <= stride;
-}
 
 // Per-task worker: one stream + staging buffers, leased per host thread.
 struct TaskWorker {
@@ -466,7 +462,6 @@ struct swh_gspace {
   // the record the step kernel reduces into and its pinned copy
   swh_gpart_step_layout step_layout{-1, -1, -1, -1};
   bool step_layout_set = false;
-  bool step_checked = false;   // every offset the step kernels use lies inside the stride
   bool tree_stale = false;     // drifted since the tree was installed (swh_gspace_drift)
   swh::StepRecord gstep{swh::kRecStrideGspace};
   // drift, init_grav, end_force, kick / timestep / end_step (swh_gspace_step_times)

@@ -17,6 +17,7 @@
 #include <cfloat>
 
 #include "swh_internal.h"
+#include "swh_grec.h"
 #include "swh_rms.h"
 #include "swh_space.h"
 #include "swh_wave.h"
@@ -33,11 +34,6 @@ static_assert(sizeof(swh_displacement_sums) == 24 &&
 
 // One block per CU at most, as the statistics (65,536 particles per pass).
 constexpr int kRmsBlocks = 256;
-
-// every offset of a gpart record these kernels read
-struct GRmsLayout {
-  int stride, v_full, mass, time_bin, type;
-};
 
 __device__ __forceinline__ float wave_min_f(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
@@ -114,11 +110,10 @@ __global__ __launch_bounds__(256) void space_rms_kernel(SoA a, int64_t n,
   rms_commit(sum, mn, cnt, partials);
 }
 
-// STD: the multi-softening record (swh_gkick.hip's GRec): v_full in bytes
-// 32..44 of an aligned 16-byte piece, mass at 76, {time_bin, type} at 88
+// One 16-byte piece (STD) or v_full, and two words: {time_bin, type}, mass.
 template <bool STD>
 __global__ __launch_bounds__(256) void gspace_rms_kernel(
-    GRmsLayout L, const char* __restrict__ aos, int64_t n,
+    GRecLayout L, const char* __restrict__ aos, int64_t n,
     swh_displacement_sums* __restrict__ partials) {
   double sum = 0.;
   float mn = FLT_MAX;
@@ -126,28 +121,13 @@ __global__ __launch_bounds__(256) void gspace_rms_kernel(
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
        s += (int64_t)gridDim.x * blockDim.x) {
     const char* r = aos + s * L.stride;
-    int bin, type;
-    if (STD) {
-      const int bits = *reinterpret_cast<const int*>(r + 88);
-      bin = (int)(int8_t)(bits & 0xff);
-      type = (int)(int8_t)((bits >> 8) & 0xff);
-    } else {
-      bin = *reinterpret_cast<const int8_t*>(r + L.time_bin);
-      type = *reinterpret_cast<const int8_t*>(r + L.type);
-    }
-    if (type != 1 || !stats_bin_exists(bin)) continue;  // dark matter only
-    float v[3], m;
-    if (STD) {
-      const float4 q = *reinterpret_cast<const float4*>(r + 32);
-      v[0] = q.x, v[1] = q.y, v[2] = q.z;
-      m = *reinterpret_cast<const float*>(r + 76);
-    } else {
-      const float* f = reinterpret_cast<const float*>(r + L.v_full);
-      v[0] = f[0], v[1] = f[1], v[2] = f[2];
-      m = *reinterpret_cast<const float*>(r + L.mass);
-    }
-    sum += (double)rms_vel_norm(v[0], v[1], v[2]);
-    mn = fminf(mn, m);
+    GRec<STD> g;
+    g.template load_fields<GF_TIME_BIN | GF_TYPE>(L, r);
+    if (g.type != 1 || !stats_bin_exists(g.bin)) continue;  // dark matter only
+    g.template load<GF_V_FULL>(L, r);
+    g.template load_fields<GF_MASS>(L, r);
+    sum += (double)rms_vel_norm(g.v[0], g.v[1], g.v[2]);
+    mn = fminf(mn, g.mass);
     cnt++;
   }
   rms_commit(sum, mn, cnt, partials);
@@ -206,38 +186,6 @@ static swh_status rms_result(RmsState& S, swh_displacement_sums* out, const char
   return SWH_OK;
 }
 
-// The order of the checks is swh_gkick.hip's step_ready: upload, step layout,
-// then every offset these kernels use against the stride.
-static swh_status gspace_rms_ready(swh_gspace* g, const char* what, GRmsLayout* out) {
-  if (!g->uploaded) {
-    set_error("swh_gspace_upload must precede %s", what);
-    return SWH_ERR_STATE;
-  }
-  if (!g->step_layout_set) {
-    set_error("swh_gspace_set_step_layout must precede %s", what);
-    return SWH_ERR_STATE;
-  }
-  if (g->n == 0) return SWH_OK;
-  const GLayout& G = g->layout;
-  const swh_gpart_step_layout& S = g->step_layout;
-  const GRmsLayout L{G.stride, S.off_v_full, G.mass, G.time_bin, S.off_type};
-  if (L.stride <= 0 || L.stride % 4 != 0 || !float_field_ok(L.v_full, 3, L.stride) ||
-      !float_field_ok(L.mass, 1, L.stride) || L.time_bin < 0 || L.time_bin >= L.stride ||
-      L.type < 0 || L.type >= L.stride) {
-    set_error("%s: v_full, mass, time_bin and type must lie inside the gpart record of %d bytes, "
-              "aligned to their type", what, L.stride);
-    return SWH_ERR_ARG;
-  }
-  *out = L;
-  return SWH_OK;
-}
-
-// the multi-softening record: the 16-byte route (swh_gkick.hip's is_std_layout)
-static bool is_std_layout(const GRmsLayout& L, const void* aos) {
-  return L.stride == 96 && L.v_full == 32 && L.mass == 76 && L.time_bin == 88 && L.type == 89 &&
-         reinterpret_cast<uintptr_t>(aos) % 16 == 0;
-}
-
 }  // namespace swh
 
 using namespace swh;
@@ -267,21 +215,18 @@ swh_status swh_space_displacement_sums_result(swh_space* s, swh_displacement_sum
 
 swh_status swh_gspace_displacement_sums(swh_gspace* g) {
   if (!g) return SWH_ERR_ARG;
-  GRmsLayout L{};
-  SWH_TRY(gspace_rms_ready(g, "swh_gspace_displacement_sums", &L));
+  GRecLayout L;
+  SWH_TRY(gspace_record(g, kNeedRms, "swh_gspace_displacement_sums", &L));
   SWH_HIP(hipSetDevice(g->ctx->device));
   if (g->n == 0) return rms_empty(g->rms);
   hipStream_t st = g->stream;
   const int grid = rms_grid(g->n);
   SWH_TRY(rms_prepare(g->rms, grid));
-  if (is_std_layout(L, g->aos.ptr))
-    hipLaunchKernelGGL(gspace_rms_kernel<true>, dim3(grid), dim3(256), 0, st, L,
+  grec_dispatch(grec_is_std(L, g->aos.ptr), [&](auto STD) {
+    hipLaunchKernelGGL(gspace_rms_kernel<decltype(STD)::value>, dim3(grid), dim3(256), 0, st, L,
                        g->aos.as<const char>(), g->n,
                        g->rms.partials.as<swh_displacement_sums>());
-  else
-    hipLaunchKernelGGL(gspace_rms_kernel<false>, dim3(grid), dim3(256), 0, st, L,
-                       g->aos.as<const char>(), g->n,
-                       g->rms.partials.as<swh_displacement_sums>());
+  });
   SWH_HIP(hipGetLastError());
   return rms_finish(g->rms, grid, st);
 }

@@ -17,6 +17,7 @@
 #include <algorithm>
 
 #include "swh_internal.h"
+#include "swh_grec.h"
 #include "swh_space.h"
 #include "swh_stats.h"
 #include "swh_wave.h"
@@ -45,11 +46,6 @@ struct StatsDev {
   float dt_mesh, a_inv, a_factor_u;
   int periodic;
   double dim[3];
-};
-
-// every offset of a gpart record these kernels read
-struct GStatsLayout {
-  int stride, x, v_full, a_grav, a_grav_mesh, potential, mass, time_bin, type;
 };
 
 // A lane's sums into its block's record; every thread of a 256-thread block
@@ -182,46 +178,14 @@ __global__ __launch_bounds__(256) void space_sync_velocity_kernel(SoA a, SpaceSt
   }
 }
 
-// What the kernels read of a gpart record. STD: the multi-softening record,
-// bytes 32..96 as four 16-byte pieces (swh_gkick.hip's GRec).
+// convert_gpart_vel of a loaded record
 template <bool STD>
-struct GStatRec {
-  double x[3];
-  float v[3], a[3], am[3], pot, mass;
-  int bin, type;
-  __device__ __forceinline__ void load(const GStatsLayout& L, const char* r) {
-    const double* xp = reinterpret_cast<const double*>(r + (STD ? 8 : L.x));
-    x[0] = xp[0], x[1] = xp[1], x[2] = xp[2];
-    if (STD) {
-      const float4* p = reinterpret_cast<const float4*>(r + 32);
-      const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-      v[0] = q0.x, v[1] = q0.y, v[2] = q0.z;
-      a[0] = q0.w, a[1] = q1.x, a[2] = q1.y;
-      am[0] = q1.z, am[1] = q1.w, am[2] = q2.x;
-      pot = q2.y, mass = q2.w;
-      const int bits = __float_as_int(q3.z);  // time_bin, type, padding
-      bin = (int)(int8_t)(bits & 0xff);
-      type = (int)(int8_t)((bits >> 8) & 0xff);
-    } else {
-      const float* f = reinterpret_cast<const float*>(r + L.v_full);
-      v[0] = f[0], v[1] = f[1], v[2] = f[2];
-      f = reinterpret_cast<const float*>(r + L.a_grav);
-      a[0] = f[0], a[1] = f[1], a[2] = f[2];
-      f = reinterpret_cast<const float*>(r + L.a_grav_mesh);
-      am[0] = f[0], am[1] = f[1], am[2] = f[2];
-      pot = *reinterpret_cast<const float*>(r + L.potential);
-      mass = *reinterpret_cast<const float*>(r + L.mass);
-      bin = *reinterpret_cast<const int8_t*>(r + L.time_bin);
-      type = *reinterpret_cast<const int8_t*>(r + L.type);
-    }
-  }
-  __device__ __forceinline__ void sync_v(const StatsDev& P, float out[3]) const {
-    stats_gpart_velocity(out, v, a, am, P.dt_grav[kick_bin(bin)], P.dt_mesh, P.a_inv);
-  }
-};
+__device__ __forceinline__ void gspace_sync_v(const GRec<STD>& g, const StatsDev& P, float v[3]) {
+  stats_gpart_velocity(v, g.v, g.a, g.am, P.dt_grav[kick_bin(g.bin)], P.dt_mesh, P.a_inv);
+}
 
 template <bool STD>
-__global__ __launch_bounds__(256) void gspace_stats_kernel(GStatsLayout L,
+__global__ __launch_bounds__(256) void gspace_stats_kernel(GRecLayout L,
                                                            const char* __restrict__ aos, int64_t n,
                                                            StatsDev P,
                                                            double* __restrict__ partials) {
@@ -231,11 +195,11 @@ __global__ __launch_bounds__(256) void gspace_stats_kernel(GStatsLayout L,
   unsigned long long cnt = 0;
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
        s += (int64_t)gridDim.x * blockDim.x) {
-    GStatRec<STD> g;
-    g.load(L, aos + s * L.stride);
+    GRec<STD> g;
+    g.template load<kNeedStats>(L, aos + s * L.stride);
     if (!stats_bin_exists(g.bin)) continue;
     float v[3];
-    g.sync_v(P, v);
+    gspace_sync_v(g, P, v);
     double t[ST_FIELDS];
     const bool counted =
         stats_gpart_terms(t, g.type, g.mass, g.x, v, g.pot, P.a_inv, P.periodic, P.dim);
@@ -248,16 +212,16 @@ __global__ __launch_bounds__(256) void gspace_stats_kernel(GStatsLayout L,
 
 // out: n x 3 floats in record order
 template <bool STD>
-__global__ __launch_bounds__(256) void gspace_sync_velocity_kernel(GStatsLayout L,
+__global__ __launch_bounds__(256) void gspace_sync_velocity_kernel(GRecLayout L,
                                                                    const char* __restrict__ aos,
                                                                    int64_t n, StatsDev P,
                                                                    float* __restrict__ out) {
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n;
        s += (int64_t)gridDim.x * blockDim.x) {
-    GStatRec<STD> g;
-    g.load(L, aos + s * L.stride);
+    GRec<STD> g;
+    g.template load<GF_V_FULL | GF_A_GRAV | GF_A_GRAV_MESH | GF_TIME_BIN>(L, aos + s * L.stride);
     float v[3] = {0.f, 0.f, 0.f};
-    if (stats_bin_exists(g.bin)) g.sync_v(P, v);
+    if (stats_bin_exists(g.bin)) gspace_sync_v(g, P, v);
     float* o = out + (size_t)s * 3;
     o[0] = v[0];
     o[1] = v[1];
@@ -377,43 +341,6 @@ static swh_status space_stats_ready(swh_space* s, const char* what, SpaceStatsAr
   return SWH_OK;
 }
 
-// The order of the checks is swh_gkick.hip's step_ready: upload, step layout,
-// then every offset these kernels use against the stride.
-static swh_status gspace_stats_ready(swh_gspace* g, const char* what, GStatsLayout* out) {
-  if (!g->uploaded) {
-    set_error("swh_gspace_upload must precede %s", what);
-    return SWH_ERR_STATE;
-  }
-  if (!g->step_layout_set) {
-    set_error("swh_gspace_set_step_layout must precede %s", what);
-    return SWH_ERR_STATE;
-  }
-  if (g->n == 0) return SWH_OK;
-  const GLayout& G = g->layout;
-  const swh_gpart_step_layout& S = g->step_layout;
-  const GStatsLayout L{G.stride,    G.x,    S.off_v_full, G.a_grav,  S.off_a_grav_mesh,
-                       G.potential, G.mass, G.time_bin,   S.off_type};
-  // (x is read as doubles: its offset and the stride keep every record's 8-byte aligned)
-  if (L.stride <= 0 || L.stride % 8 != 0 || L.x < 0 || L.x % 8 != 0 || L.x + 24 > L.stride ||
-      !float_field_ok(L.v_full, 3, L.stride) || !float_field_ok(L.a_grav, 3, L.stride) ||
-      !float_field_ok(L.a_grav_mesh, 3, L.stride) || !float_field_ok(L.potential, 1, L.stride) ||
-      !float_field_ok(L.mass, 1, L.stride) || L.time_bin < 0 || L.time_bin >= L.stride ||
-      L.type < 0 || L.type >= L.stride) {
-    set_error("%s: x, v_full, a_grav, a_grav_mesh, potential, mass, time_bin and type must lie "
-              "inside the gpart record of %d bytes, aligned to their type", what, L.stride);
-    return SWH_ERR_ARG;
-  }
-  *out = L;
-  return SWH_OK;
-}
-
-// the multi-softening record: the 16-byte route (swh_gkick.hip's is_std_layout)
-static bool is_std_layout(const GStatsLayout& L, const void* aos) {
-  return L.stride == 96 && L.x == 8 && L.v_full == 32 && L.a_grav == 44 && L.a_grav_mesh == 56 &&
-         L.potential == 68 && L.mass == 76 && L.time_bin == 88 && L.type == 89 &&
-         reinterpret_cast<uintptr_t>(aos) % 16 == 0;
-}
-
 }  // namespace swh
 
 using namespace swh;
@@ -476,20 +403,18 @@ swh_status swh_gspace_statistics(swh_gspace* g, const swh_stats_params* P) {
   if (!g || !P) return SWH_ERR_ARG;
   StatsDev d;
   SWH_TRY(fill_stats(P, "swh_gspace_statistics", &d));
-  GStatsLayout L{};
-  SWH_TRY(gspace_stats_ready(g, "swh_gspace_statistics", &L));
+  GRecLayout L;
+  SWH_TRY(gspace_record(g, kNeedStats, "swh_gspace_statistics", &L));
   SWH_HIP(hipSetDevice(g->ctx->device));
   if (g->n == 0) return stats_zero(g->stats);
   hipStream_t st = g->stream;
   const int grid = stats_grid(g->n);
   SWH_TRY(stats_prepare(g->stats, grid));
   SWH_TRY(g->stats.timer.begin(ST_T_STATS, st));
-  if (is_std_layout(L, g->aos.ptr))
-    hipLaunchKernelGGL(gspace_stats_kernel<true>, dim3(grid), dim3(256), 0, st, L,
+  grec_dispatch(grec_is_std(L, g->aos.ptr), [&](auto STD) {
+    hipLaunchKernelGGL(gspace_stats_kernel<decltype(STD)::value>, dim3(grid), dim3(256), 0, st, L,
                        g->aos.as<const char>(), g->n, d, g->stats.partials.as<double>());
-  else
-    hipLaunchKernelGGL(gspace_stats_kernel<false>, dim3(grid), dim3(256), 0, st, L,
-                       g->aos.as<const char>(), g->n, d, g->stats.partials.as<double>());
+  });
   SWH_HIP(hipGetLastError());
   return stats_finish(g->stats, grid, st);
 }
@@ -505,8 +430,8 @@ swh_status swh_gspace_sync_velocities(swh_gspace* g, const swh_stats_params* P, 
   if (!g || !P || (g->n > 0 && !v)) return SWH_ERR_ARG;
   StatsDev d;
   SWH_TRY(fill_stats(P, "swh_gspace_sync_velocities", &d));
-  GStatsLayout L{};
-  SWH_TRY(gspace_stats_ready(g, "swh_gspace_sync_velocities", &L));
+  GRecLayout L;
+  SWH_TRY(gspace_record(g, kNeedStats, "swh_gspace_sync_velocities", &L));
   if (g->n == 0) return SWH_OK;
   SWH_HIP(hipSetDevice(g->ctx->device));
   hipStream_t st = g->stream;
@@ -514,12 +439,10 @@ swh_status swh_gspace_sync_velocities(swh_gspace* g, const swh_stats_params* P, 
   SWH_TRY(vel_target(g->stats, g->n, v, on_device, &dst));
   const int grid = stats_grid(g->n);
   SWH_TRY(g->stats.timer.begin(ST_T_VEL, st));
-  if (is_std_layout(L, g->aos.ptr))
-    hipLaunchKernelGGL(gspace_sync_velocity_kernel<true>, dim3(grid), dim3(256), 0, st, L,
-                       g->aos.as<const char>(), g->n, d, dst);
-  else
-    hipLaunchKernelGGL(gspace_sync_velocity_kernel<false>, dim3(grid), dim3(256), 0, st, L,
-                       g->aos.as<const char>(), g->n, d, dst);
+  grec_dispatch(grec_is_std(L, g->aos.ptr), [&](auto STD) {
+    hipLaunchKernelGGL(gspace_sync_velocity_kernel<decltype(STD)::value>, dim3(grid), dim3(256), 0,
+                       st, L, g->aos.as<const char>(), g->n, d, dst);
+  });
   SWH_HIP(hipGetLastError());
   return vel_deliver(g->stats, g->n, v, on_device, st);
 }

@@ -43,7 +43,7 @@ int main(int argc, char** argv) {
   if (fread(g.data(), sizeof(Gpart), P.ng, f) != (size_t)P.ng) return 5;
   if (fread(p.data(), sizeof(Part), P.n, f) != (size_t)P.n) return 5;
   fclose(f);
-  const swh::CoupleLayout L{96, 0, 8, 32, 44, 56, 88, 89};
+  const swh::GRecLayout L{96, 0, 8, 32, 44, 56, 68, 72, 76, 80, 84, 88, 89};
   std::vector<Out> out(P.ng);
   for (int k = 0; k < P.ng; k++) {
     char* r = reinterpret_cast<char*>(&g[k]);

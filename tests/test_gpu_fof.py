@@ -335,6 +335,38 @@ def test_left_out_gparts_do_not_bridge(gpu_ctx):
         assert up_roots[bridges["live"]] >= 0 and up_ids[bridges["live"]] == 1
 
 
+def test_no_step_layout_no_type_field(gpu_ctx):
+    """A gspace without a step layout has no type field: every live gpart
+    links. With no neutrino in the set that is the typed search's answer:
+    same groups, sizes and ids, both the reference's."""
+    from swift_subtask_dev_amd import lib
+    x = RF.clump_positions(11)[np.r_[0:60, 400:460, 700:740, 1250:1347]]
+    g = gparts_of(x)
+    n = len(g)
+    assert n == 257
+    g["type"] = np.random.Generator(np.random.PCG64(5)).choice([0, 1, 1, 2, 4], n)
+    g["time_bin"][::17] = abi.TIME_BIN_INHIBITED
+    out = []
+    for step_layout in (True, False):
+        gs = lib.GravSpace(gpu_ctx, step_layout=step_layout)
+        gs.upload(abi.copy_parts(g))
+        gs.build_tree(2, 16)
+        res = gs.fof(abi.FofParams(L_X * L_X, 1))
+        raw = abi.new_gparts(n)
+        gs.download(raw)
+        gs.close()
+        check_against(res, RF.of_gparts(raw, L_X * L_X, 1), f"step layout {step_layout}")
+        out.append((res, raw))
+    (a, raw_a), (b, raw_b) = out
+    assert np.array_equal(raw_a.view(np.uint8), raw_b.view(np.uint8))
+    assert a["n_groups"] >= 3 and a["max_group_size"] >= 30
+    assert a["n_linkable"] == n - len(range(0, n, 17))
+    for k in ("roots", "group_ids"):
+        assert np.array_equal(a[k], b[k]), k
+    for k in ("size", "root", "mass", "com"):
+        assert np.array_equal(a["groups"][k], b["groups"][k]), k
+
+
 # ------------------------------------------------ 7. centre of mass at a face
 def test_centre_of_mass_across_a_face(gpu_ctx):
     rng = np.random.Generator(np.random.PCG64(44))

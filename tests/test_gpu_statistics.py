@@ -339,6 +339,41 @@ def test_gspace_sums_above_one_grid_pass(gpu_ctx):
     gs.close()
 
 
+@pytest.mark.parametrize("n", [1, 65, 257])
+def test_gspace_field_by_field_route(gpu_ctx, n):
+    """The same records on two gspaces: one with the standard step layout (the
+    16-byte route), one whose potential_mesh offset points at mass, which is no
+    standard record any more (field by field; these kernels do not read
+    potential_mesh). Both routes add the same terms in the same order: equal
+    sums field for field, equal velocity bits, both within the bound of the
+    restatement, no record byte written."""
+    from swift_subtask_dev_amd import lib
+    _, gp = ics.small_cosmo_volume(8)
+    g = random_gparts(gp[:n])
+    if n == 1:
+        g["time_bin"][0], g["type"][0] = 7, 1  # (random_gparts inhibits record 0)
+    else:
+        assert len(set(g["type"])) == 5 and (g["time_bin"] == abi.TIME_BIN_INHIBITED).any()
+        assert (g["time_bin"] == abi.TIME_BIN_NOT_CREATED).any()
+    std = lib.GravSpace(gpu_ctx)
+    std.upload(abi.copy_parts(g))
+    gen = lib.GravSpace(gpu_ctx, step_layout=False)
+    gen.upload(abi.copy_parts(g))
+    SL = abi.gpart_step_layout()
+    SL.off_potential_mesh = abi.GPART_DTYPE.fields["mass"][1]
+    gen.set_step_layout(SL)
+    for name, S in modes().items():
+        a = check_gspace(std, n, S, f"16-byte n={n} {name}")
+        b = check_gspace(gen, n, S, f"field by field n={n} {name}")
+        for k in RS.NAMES:
+            assert same(a[k], b[k]), (name, k, a[k], b[k])
+        assert a["n_counted"] == b["n_counted"]
+        assert same(std.sync_velocities(S.abi()), gen.sync_velocities(S.abi())), name
+    for gs in (std, gen):
+        assert KC.same_records(gfetch(gs, n)[1], g)
+        gs.close()
+
+
 # -------------------------------------------------------------- 3. ownership
 def test_owned_halves_add_to_the_whole(gpu_ctx):
     from swift_subtask_dev_amd import lib
