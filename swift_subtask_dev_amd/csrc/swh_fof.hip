@@ -490,21 +490,6 @@ __global__ __launch_bounds__(256) void fof_group_wave_kernel(
 // Host side
 // ---------------------------------------------------------------------------
 
-// Grow a device buffer keeping its first `used` bytes.
-static swh_status fof_grow_keep(DevBuf& b, size_t need, size_t used, hipStream_t st) {
-  if (need <= b.bytes) return SWH_OK;
-  DevBuf nb;
-  SWH_TRY(nb.reserve(std::max(need, 2 * b.bytes)));
-  if (used > 0) SWH_HIP(hipMemcpyAsync(nb.ptr, b.ptr, used, hipMemcpyDeviceToDevice, st));
-  SWH_HIP(hipStreamSynchronize(st));
-  b.release();
-  b.ptr = nb.ptr;
-  b.bytes = nb.bytes;
-  nb.ptr = nullptr;
-  nb.bytes = 0;
-  return SWH_OK;
-}
-
 // the first `count` counters to the pinned copy, and wait
 static swh_status fof_read_counters(FofState& F, int count, hipStream_t st) {
   SWH_HIP(hipMemcpyAsync(F.host.ptr, F.ctr.ptr, (size_t)count * sizeof(unsigned long long),
@@ -568,8 +553,8 @@ static swh_status fof_walk(swh_gspace* g, FofState& F, const FofDev& P, hipStrea
     }
     const size_t bound = (size_t)n_self * 36 + (size_t)(n_cur - n_self) * 8;
     SWH_TRY(nxt->reserve(std::max<size_t>(1, bound) * sizeof(int2)));
-    SWH_TRY(fof_grow_keep(F.lpairs, (size_t)(n_lp + n_cur) * sizeof(int2),
-                          (size_t)n_lp * sizeof(int2), st));
+    SWH_TRY(F.lpairs.grow_keep((size_t)(n_lp + n_cur) * sizeof(int2), (size_t)n_lp * sizeof(int2),
+                             st));
     SWH_HIP(hipMemsetAsync(ctr + FC_NEXT, 0, 2 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(fof_walk_kernel, dim3((unsigned)((n_cur + 255) / 256)), dim3(256), 0, st,
                        cur->as<const int2>(), (int)n_cur, cells, box, P, nxt->as<int2>(),
@@ -588,23 +573,16 @@ static swh_status fof_walk(swh_gspace* g, FofState& F, const FofDev& P, hipStrea
 template <typename K, typename V>
 static swh_status fof_sort_pairs(FofState& F, const K* kin, K* kout, const V* vin, V* vout, int n,
                                  int end_bit, hipStream_t st) {
-  size_t tb = 0;
-  SWH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, n, 0, end_bit, st));
-  SWH_TRY(F.tmp.reserve(tb));
-  tb = F.tmp.bytes;
-  SWH_HIP(hipcub::DeviceRadixSort::SortPairs(F.tmp.ptr, tb, kin, kout, vin, vout, n, 0, end_bit,
-                                             st));
-  return SWH_OK;
+  return cub_run(F.tmp, [&](void* tmp, size_t& tb) {
+    return hipcub::DeviceRadixSort::SortPairs(tmp, tb, kin, kout, vin, vout, n, 0, end_bit, st);
+  });
 }
 
 static swh_status fof_sort_keys(FofState& F, const unsigned long long* kin,
                                 unsigned long long* kout, int n, hipStream_t st) {
-  size_t tb = 0;
-  SWH_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, kin, kout, n, 0, 64, st));
-  SWH_TRY(F.tmp.reserve(tb));
-  tb = F.tmp.bytes;
-  SWH_HIP(hipcub::DeviceRadixSort::SortKeys(F.tmp.ptr, tb, kin, kout, n, 0, 64, st));
-  return SWH_OK;
+  return cub_run(F.tmp, [&](void* tmp, size_t& tb) {
+    return hipcub::DeviceRadixSort::SortKeys(tmp, tb, kin, kout, n, 0, 64, st);
+  });
 }
 
 static swh_status fof_ready(swh_gspace* g, const char* what, FofState** out) {

@@ -18,6 +18,9 @@
 // arithmetic of the keys is ics.gravity_tree's operation by operation (true
 // divisions, no contraction), so the table and the order equal the host
 // builder's bit for bit.
+//
+// The file also owns the bookkeeping of a cell table, built here or given by
+// the caller (gtree_install, swh_gspace_set_tree, swh_gspace_set_owned_cells).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -285,39 +288,20 @@ __global__ __launch_bounds__(kGtBlock) void gtree_leaf_of_kernel(
 
 static inline int gt_grid(int64_t n) { return (int)((n + kGtBlock - 1) / kGtBlock); }
 
-// Grow a buffer whose first `used` bytes are live.
-static swh_status gt_grow_keep(DevBuf& b, size_t need, size_t used, hipStream_t stream) {
-  if (need <= b.bytes) return SWH_OK;
-  DevBuf nb;
-  SWH_TRY(nb.reserve(std::max(need, 2 * b.bytes)));
-  if (used > 0) {
-    SWH_HIP(hipMemcpyAsync(nb.ptr, b.ptr, used, hipMemcpyDeviceToDevice, stream));
-    SWH_HIP(hipStreamSynchronize(stream));
-  }
-  b.release();
-  b = nb;
-  return SWH_OK;
-}
-
 template <typename K>
 static swh_status gt_sort_pairs(swh_gspace* g, const K* kin, K* kout, const int* vin, int* vout,
                                 int n, int end_bit) {
-  size_t tb = 0;
-  SWH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, n, 0, end_bit,
-                                             g->stream));
-  SWH_TRY(g->gt_tmp.reserve(std::max<size_t>(tb, 1)));
-  SWH_HIP(hipcub::DeviceRadixSort::SortPairs(g->gt_tmp.ptr, tb, kin, kout, vin, vout, n, 0,
-                                             end_bit, g->stream));
-  return SWH_OK;
+  return cub_run(g->gt_tmp, [&](void* tmp, size_t& tb) {
+    return hipcub::DeviceRadixSort::SortPairs(tmp, tb, kin, kout, vin, vout, n, 0, end_bit,
+                                              g->stream);
+  });
 }
 
 // out[0 .. n] = exclusive scan of in[0 .. n] (in[n] = 0: out[n] is the total)
 static swh_status gt_scan(swh_gspace* g, const int* in, int* out, int n1) {
-  size_t tb = 0;
-  SWH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n1, g->stream));
-  SWH_TRY(g->gt_tmp.reserve(std::max<size_t>(tb, 1)));
-  SWH_HIP(hipcub::DeviceScan::ExclusiveSum(g->gt_tmp.ptr, tb, in, out, n1, g->stream));
-  return SWH_OK;
+  return cub_run(g->gt_tmp, [&](void* tmp, size_t& tb) {
+    return hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, n1, g->stream);
+  });
 }
 
 static int gt_bits(uint64_t v) {  // bits needed for values 0 .. v
@@ -479,7 +463,7 @@ swh_status swh_gspace_build_tree(swh_gspace* g, const swh_tree_params* T, int32_
   SWH_HIP(hipMemsetAsync(g->accel.ptr, 0, N * sizeof(double4), st));
 
   // room for the usual tree; a deeper one grows the table level by level
-  SWH_TRY(gt_grow_keep(g->gt_bcell, ((size_t)ntops + N / 4 + 1024) * sizeof(BCell), 0, st));
+  SWH_TRY(g->gt_bcell.grow_keep(((size_t)ntops + N / 4 + 1024) * sizeof(BCell), 0, st));
   hipLaunchKernelGGL(gtree_top_write_kernel, dim3(gt_grid(ntop)), dim3(kGtBlock), 0, st, ntop,
                      cdim, w, g->gt_tstart.as<const int>(), g->gt_scan.as<const int>(),
                      g->gt_bcell.as<BCell>());
@@ -503,7 +487,7 @@ swh_status swh_gspace_build_tree(swh_gspace* g, const swh_tree_params* T, int32_
       set_error("build_tree: more than %d cells", INT32_MAX / 2);
       return SWH_ERR_ARG;
     }
-    SWH_TRY(gt_grow_keep(g->gt_bcell, (size_t)(f1 + nchild) * sizeof(BCell),
+    SWH_TRY(g->gt_bcell.grow_keep((size_t)(f1 + nchild) * sizeof(BCell),
                          (size_t)f1 * sizeof(BCell), st));
     hipLaunchKernelGGL(gtree_split_write_kernel, dim3(grid), dim3(kGtBlock), 0, st,
                        g->gt_bcell.as<BCell>(), f0, f1, mort_s, level, T->split_size,
@@ -593,4 +577,186 @@ swh_status swh_gspace_tree_order(swh_gspace* g, int32_t* order) {
   return SWH_OK;
 }
 
+}  // extern "C"
+
+namespace swh {
+
+// The bookkeeping of a cell table: checks, parents, the depth-grouped L2L and
+// M2M lists, the leaf ids and leaf_of. swh_gspace_set_tree takes the caller's
+// table (leaf_of filled on the host and uploaded, the table copied to tree_d);
+// swh_gspace_build_tree's is already in tree_d and a kernel fills leaf_of.
+swh_status gtree_install(swh_gspace* g, const swh_gcell* cells, int32_t ncells,
+                         bool device_built) {
+  g->mpoles_given = false;
+  g->tree_stale = false;
+  std::vector<int> parent(ncells, -1);
+  for (int c = 0; c < ncells; c++) {
+    const swh_gcell& C = cells[c];
+    if (C.start < 0 || C.count <= 0 || C.start + C.count > g->n) {
+      set_error("cell %d [%d,+%d) empty or outside the gpart set of %lld", c, C.start, C.count,
+                (long long)g->n);
+      return SWH_ERR_ARG;
+    }
+    if (C.split) {
+      // m2m_kernel bounds r_max by the CoM's distance to the farthest
+      // corner of [loc, loc + width] (space_split.c:419-433): a split cell
+      // needs real geometry, and its progeny must lie inside it
+      if (!(C.width[0] > 0. && C.width[1] > 0. && C.width[2] > 0.)) {
+        set_error("cell %d is split but its width (%g, %g, %g) is not positive", c, C.width[0],
+                  C.width[1], C.width[2]);
+        return SWH_ERR_ARG;
+      }
+      int64_t sum = 0;
+      for (int k = 0; k < 8; k++) {
+        const int p = C.progeny[k];
+        if (p < 0) continue;
+        if (p >= ncells || p == c || parent[p] >= 0) {
+          set_error("cell %d: bad progeny %d", c, p);
+          return SWH_ERR_ARG;
+        }
+        const swh_gcell& P = cells[p];
+        if (P.start < C.start || P.start + P.count > C.start + C.count) {
+          set_error("cell %d: progeny %d outside its range", c, p);
+          return SWH_ERR_ARG;
+        }
+        for (int a = 0; a < 3; a++) {
+          const double tol = 1e-12 * C.width[a];
+          if (P.loc[a] < C.loc[a] - tol || P.loc[a] + P.width[a] > C.loc[a] + C.width[a] + tol) {
+            set_error("cell %d: progeny %d box outside the cell's box (axis %d)", c, p, a);
+            return SWH_ERR_ARG;
+          }
+        }
+        parent[p] = c;
+        sum += P.count;
+      }
+      if (sum != C.count) {
+        set_error("cell %d: progeny hold %lld of its %d gparts", c, (long long)sum, C.count);
+        return SWH_ERR_ARG;
+      }
+    }
+  }
+  // depth of every cell (roots: no parent), L2L list grouped by depth
+  std::vector<int> depth(ncells, -1);
+  int maxd = 0;
+  for (int c = 0; c < ncells; c++) {
+    int d = 0, x = c;
+    while (parent[x] >= 0) {
+      x = parent[x];
+      d++;
+      if (d > ncells) {
+        set_error("cell tree has a cycle");
+        return SWH_ERR_ARG;
+      }
+    }
+    depth[c] = d;
+    maxd = std::max(maxd, d);
+  }
+  std::vector<int2> l2l;
+  std::vector<int32_t> doff(1, 0);
+  for (int d = 1; d <= maxd; d++) {
+    for (int c = 0; c < ncells; c++)
+      if (depth[c] == d) l2l.push_back(make_int2(c, parent[c]));
+    doff.push_back((int32_t)l2l.size());
+  }
+  // the upward pass: split cells, deepest first (M2M reads finished progeny)
+  std::vector<int> m2m;
+  std::vector<int32_t> moff(1, 0);
+  for (int d = maxd; d >= 0; d--) {
+    for (int c = 0; c < ncells; c++)
+      if (depth[c] == d && cells[c].split) m2m.push_back(c);
+    moff.push_back((int32_t)m2m.size());
+  }
+  std::vector<int> leaves;
+  std::vector<swh_leaf> ranges(ncells);
+  // gpart -> its leaf cell (L2P)
+  std::vector<int> leaf_of(device_built ? (size_t)0 : (size_t)g->n, -1);
+  for (int c = 0; c < ncells; c++) {
+    if (!cells[c].split) {
+      leaves.push_back(c);
+      if (!device_built)
+        for (int k = cells[c].start; k < cells[c].start + cells[c].count; k++) leaf_of[k] = c;
+    }
+    ranges[c] = swh_leaf{cells[c].start, cells[c].count};
+  }
+  // the cell table doubles as the P2P kernels' leaf table (pairs set later)
+  std::vector<int32_t> off(ncells + 1, 0);
+  SWH_TRY(swh_gspace_set_leaves(g, ranges.data(), ncells, off.data(), nullptr, 0));
+  SWH_HIP(hipSetDevice(g->ctx->device));
+  if (cells != g->tree.data()) g->tree.assign(cells, cells + ncells);
+  g->tree_parent = parent;
+  g->tree_tops.clear();
+  for (int c = 0; c < ncells; c++)
+    if (parent[c] < 0) g->tree_tops.push_back(c);
+  g->owned.clear();
+  SWH_TRY(g->cell_act.reserve((size_t)std::max(1, ncells)));
+  SWH_TRY(g->ftens.reserve((size_t)std::max(1, ncells) * SWH_MPOLE_TERMS * sizeof(double)));
+  SWH_TRY(g->l2l_list.reserve(std::max<size_t>(1, l2l.size()) * sizeof(int2)));
+  SWH_TRY(g->leaf_ids.reserve(std::max<size_t>(1, leaves.size()) * sizeof(int)));
+  SWH_TRY(g->leaf_of.reserve(std::max<size_t>(1, (size_t)g->n) * sizeof(int)));
+  SWH_TRY(g->m2m_list.reserve(std::max<size_t>(1, m2m.size()) * sizeof(int)));
+  if (!m2m.empty())
+    SWH_HIP(hipMemcpyAsync(g->m2m_list.ptr, m2m.data(), m2m.size() * sizeof(int),
+                           hipMemcpyHostToDevice, g->stream));
+  if (!leaf_of.empty())
+    SWH_HIP(hipMemcpyAsync(g->leaf_of.ptr, leaf_of.data(), leaf_of.size() * sizeof(int),
+                           hipMemcpyHostToDevice, g->stream));
+  if (!l2l.empty())
+    SWH_HIP(hipMemcpyAsync(g->l2l_list.ptr, l2l.data(), l2l.size() * sizeof(int2),
+                           hipMemcpyHostToDevice, g->stream));
+  if (!leaves.empty())
+    SWH_HIP(hipMemcpyAsync(g->leaf_ids.ptr, leaves.data(), leaves.size() * sizeof(int),
+                           hipMemcpyHostToDevice, g->stream));
+  SWH_HIP(hipStreamSynchronize(g->stream));
+  g->l2l_depth_off = doff;
+  g->m2m_depth_off = moff;
+  g->nleaf_cells = (int32_t)leaves.size();
+  int32_t ml = 0;
+  for (int c : leaves) ml = std::max(ml, cells[c].count);
+  g->tree_max_leaf = ml;
+  if (device_built) return gtree_fill_leaf_of(g, ncells);
+  SWH_TRY(g->tree_d.reserve((size_t)std::max(1, ncells) * sizeof(swh_gcell)));
+  if (ncells > 0) {
+    SWH_HIP(hipMemcpyAsync(g->tree_d.ptr, cells, (size_t)ncells * sizeof(swh_gcell),
+                           hipMemcpyHostToDevice, g->stream));
+    SWH_HIP(hipStreamSynchronize(g->stream));
+  }
+  return SWH_OK;
+}
+
+}  // namespace swh
+
+extern "C" {
+
+swh_status swh_gspace_set_tree(swh_gspace* g, const swh_gcell* cells, int32_t ncells) {
+  if (!g || ncells < 0 || (ncells > 0 && !cells)) return SWH_ERR_ARG;
+  return gtree_install(g, cells, ncells, false);
+}
+
+swh_status swh_gspace_set_owned_cells(swh_gspace* g, const uint8_t* owned, int32_t ncells) {
+  if (!g) return SWH_ERR_ARG;
+  if (!owned) {
+    g->owned.clear();
+    return SWH_OK;
+  }
+  if (ncells != (int32_t)g->tree.size()) {
+    set_error("set_owned_cells: %d cells, the tree has %zu (swh_gspace_set_tree first)", ncells,
+              g->tree.size());
+    return SWH_ERR_ARG;
+  }
+  for (int c = 0; c < ncells; c++) {
+    const int p = g->tree_parent[c];
+    if (p >= 0 && (owned[c] != 0) != (owned[p] != 0)) {
+      set_error("set_owned_cells: cell %d and its parent %d differ (own whole subtrees)", c, p);
+      return SWH_ERR_ARG;
+    }
+  }
+  SWH_HIP(hipSetDevice(g->ctx->device));
+  g->owned.assign(owned, owned + ncells);
+  for (auto& o : g->owned) o = o ? 1 : 0;
+  SWH_TRY(g->owned_d.reserve((size_t)std::max(1, ncells)));
+  SWH_HIP(hipMemcpyAsync(g->owned_d.ptr, g->owned.data(), (size_t)ncells, hipMemcpyHostToDevice,
+                         g->stream));
+  SWH_HIP(hipStreamSynchronize(g->stream));
+  return SWH_OK;
+}
 }  // extern "C"

@@ -62,9 +62,33 @@ struct DevBuf {
     ptr = nullptr;
     bytes = 0;
   }
+  // Grow (at least doubling) keeping the first `used` bytes; the stream is
+  // waited for before the old buffer goes, whatever work still reads it.
+  swh_status grow_keep(size_t need, size_t used, hipStream_t stream) {
+    if (need <= bytes) return SWH_OK;
+    DevBuf nb;
+    SWH_TRY(nb.reserve(need > 2 * bytes ? need : 2 * bytes));
+    if (used > 0) SWH_HIP(hipMemcpyAsync(nb.ptr, ptr, used, hipMemcpyDeviceToDevice, stream));
+    SWH_HIP(hipStreamSynchronize(stream));
+    release();
+    *this = nb;
+    return SWH_OK;
+  }
   template <typename T>
   T* as() const { return reinterpret_cast<T*>(ptr); }
 };
+
+// hipcub's two-call idiom: call(nullptr, bytes) asks for the scratch size,
+// `tmp` is grown to it, call(tmp.ptr, bytes) runs.
+template <typename Call>
+swh_status cub_run(DevBuf& tmp, Call&& call) {
+  size_t tb = 0;
+  SWH_HIP(call(nullptr, tb));
+  SWH_TRY(tmp.reserve(tb > 0 ? tb : 1));
+  tb = tmp.bytes;
+  SWH_HIP(call(tmp.ptr, tb));
+  return SWH_OK;
+}
 
 // Pinned host staging buffer.
 struct HostBuf {
@@ -479,7 +503,7 @@ void fof_release(swh_gspace* g);   // swh_fof.hip: the search's buffers, event a
 void mesh_release(swh_gspace* g);  // swh_mesh.hip: mesh buffers and hipFFT plans
 void gtree_release(swh_gspace* g);  // swh_gtree.hip: the tree build's scratch and events
 void gstep_release(swh_gspace* g);  // swh_gkick.hip: the step record and the stage timer
-// swh_grav.hip: the bookkeeping of a cell table, shared by swh_gspace_set_tree
+// swh_gtree.hip: the bookkeeping of a cell table, shared by swh_gspace_set_tree
 // and swh_gspace_build_tree. device_built: the table is already in tree_d and
 // leaf_of is filled on the device (gtree_fill_leaf_of), nothing O(N) on the host.
 swh_status gtree_install(swh_gspace* g, const swh_gcell* cells, int32_t ncells, bool device_built);

@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "swh_gwalk.h"  // MacParams, the M2L acceptance test
 #include "swh_physics.h"
 #include "swifthip.h"
 
@@ -46,28 +47,6 @@ __host__ __device__ constexpr double herm_coef(int a, int i) {
 
 // n! for n <= 4
 __host__ __device__ constexpr double fact(int n) { return n <= 1 ? 1. : n * fact(n - 1); }
-
-// MAC parameters (swh_grav_params) in the float form the reference uses.
-struct MacParams {
-  float theta_crit2, eps, r_s_inv;
-  int advanced, gadget, below_soft, trunc_mac, periodic;
-  float dim[3];
-};
-
-inline MacParams mac_params(const swh_grav_params* G) {
-  MacParams m;
-  const float th = G->theta_crit;
-  m.theta_crit2 = th * th;
-  m.eps = G->adaptive_tolerance;
-  m.r_s_inv = G->r_s_inv;
-  m.advanced = G->use_advanced_MAC;
-  m.gadget = G->use_gadget_tolerance;
-  m.below_soft = G->use_tree_below_softening;
-  m.trunc_mac = G->consider_truncation_in_MAC;
-  m.periodic = G->periodic;
-  for (int k = 0; k < 3; k++) m.dim[k] = G->dim[k];
-  return m;
-}
 
 // The multipole fields the acceptance test reads, as floats.
 struct MacSource {
@@ -477,62 +456,6 @@ __device__ __forceinline__ void l2p(const double* F, T dx, T dy, T dz, T* out) {
   out[1] = ax;
   out[2] = ay;
   out[3] = az;
-}
-
-// gravity_M2L_accept (multipole_accept.h:78-176) for sink A, source B, in the
-// reference's float arithmetic (host side: the tree walk's decision).
-struct M2LSide {
-  float rho, max_soft, min_a, M000, power[3];
-};
-__host__ __device__ inline M2LSide m2l_side(const swh_multipole& m) {
-  M2LSide s;
-  s.rho = (float)m.r_max;
-  s.max_soft = m.max_softening;
-  s.min_a = m.min_old_a_grav_norm;
-  s.M000 = m.M[0];
-  for (int k = 0; k < 3; k++) s.power[k] = m.power[k];
-  return s;
-}
-__host__ __device__ inline bool m2l_accept(const MacParams& P, const M2LSide& A, const M2LSide& B,
-                                           float r2) {
-#pragma clang fp contract(off)
-  const float rho_A = A.rho, rho_B = B.rho;
-  const float rho_max = rho_A > rho_B ? rho_A : rho_B;
-  const float max_softening = A.max_soft > B.max_soft ? A.max_soft : B.max_soft;
-  // p = 2: sum_n binomial(2, n) power_B[n] rho_A^(2 - n)
-  float E_BA_term = 0.f;
-  E_BA_term += 1.f * B.power[0] * (rho_A * rho_A);
-  E_BA_term += 2.f * B.power[1] * rho_A;
-  E_BA_term += 1.f * B.power[2] * 1.f;
-  E_BA_term *= 8.f;
-  if (rho_A + rho_B > 0.f) {
-    E_BA_term *= rho_max;
-    E_BA_term /= (rho_A + rho_B);
-  }
-  const float r_to_p = r2;
-  float f_MAC_inv = r2;
-  if (P.periodic && P.trunc_mac) {  // gravity_f_MAC_inverse
-    const float H = max_softening;
-    if (r2 < (25.f / 81.f) * H * H)
-      f_MAC_inv = (25.f / 81.f) * H * H;
-    else if (P.r_s_inv * P.r_s_inv * r2 > (25.f / 9.f))
-      f_MAC_inv = (9.f / 25.f) * P.r_s_inv * P.r_s_inv * r2 * r2;
-  }
-  const float min_a_grav = A.min_a;
-  const float M_max = A.M000 > B.M000 ? A.M000 : B.M000;
-  const float rho_sum = rho_A + rho_B;
-  const bool cond_2 = P.below_soft || max_softening * max_softening < r2;
-  if (P.advanced && P.gadget) {
-    const float q = rho_max / sqrtf(r2);
-    const float ratio = q * q * q;  // integer_powf(q, SELF_GRAVITY_MULTIPOLE_ORDER - 1)
-    return (M_max * ratio < P.eps * min_a_grav * f_MAC_inv) && cond_2;
-  }
-  if (P.advanced) {
-    const bool cond_1 = rho_sum * rho_sum < r2;
-    const bool cond_3 = E_BA_term < P.eps * min_a_grav * r_to_p * f_MAC_inv;
-    return cond_1 && cond_2 && cond_3;
-  }
-  return (rho_sum * rho_sum < P.theta_crit2 * r2) && cond_2;
 }
 
 // gravity_multipole_compute_power (multipole.h:878-972) on the stored

@@ -37,6 +37,48 @@ def clumpy_box(n=16, seed=3):
     return g0
 
 
+def periodic_params(theta=0.6):
+    """Truncated gravity with the r_cut_max skip (mesh_side_length 32: r_s =
+    1.25 box / N_mesh)."""
+    r_s = 1.25 / 32
+    return params(periodic=True, theta=theta, r_s_inv=1 / r_s, r_cut_min=0.1 * r_s,
+                  r_cut_max=4.5 * r_s)
+
+
+def mixed_activity_box():
+    """test_tree_activity_and_adaptive_mac's gparts: half of them inactive at
+    max_active_bin 1, old_a_grav_norm spread over a decade."""
+    g0 = clumpy_box(12, seed=9)
+    rng = np.random.Generator(np.random.PCG64(2))
+    g0["time_bin"] = np.where(rng.uniform(size=len(g0)) < 0.5, 2, 1)
+    g0["old_a_grav_norm"] = rng.uniform(0.5, 5.0, len(g0)).astype(np.float32)
+    return g0
+
+
+# The smallest inputs that reach every branch of the walk (swh_gwalk.h): name ->
+# (gparts, cdim, split_size, params) and the oracle's (n_m2l, n_pp_tasks,
+# n_skipped) on it. split_size 1 makes trees of single-gpart cells, whose pairs
+# take the no-cache route.
+WALK_CASES = {
+    "periodic": (lambda: (clumpy_box(14, seed=21), 4, 24, periodic_params()),
+                 (21948, 18709, 34954)),
+    "periodic_small": (lambda: (clumpy_box(8, seed=21), 4, 8, periodic_params()),
+                       (758, 4530, 3084)),
+    "newtonian": (lambda: (clumpy_box(), 2, 32, params(theta=0.5)), (91096, 31430, 0)),
+    "adaptive_mixed": (lambda: (mixed_activity_box(), 2, 24,
+                                params(theta=0.7, advanced=1, mab=1)), (4505, 44917, 0)),
+    "no_cache": (lambda: (clumpy_box(6, seed=4), 2, 1, params(theta=0.5)), (1862, 9746, 0)),
+    "no_cache_periodic": (lambda: (clumpy_box(6, seed=4), 4, 1, periodic_params()),
+                          (214, 3267, 2345)),
+}
+
+
+def walk_case(name):
+    g0, cdim, split_size, G = WALK_CASES[name][0]()
+    g, cells, tops = ics.gravity_tree(g0, cdim, split_size=split_size)
+    return g, cells, tops, ics.top_level_pairs(tops), G
+
+
 def run_oracle(g, cells, tops, pairs, G):
     st = np.zeros(6, dtype=np.int64)
     ft = np.zeros((len(cells), 35), dtype=np.float32)
@@ -183,23 +225,39 @@ def test_tree_bad_input(gpu_ctx):
     gs.close()
 
 
-def test_device_walk_equals_host_walk(gpu_ctx, monkeypatch):
+@pytest.mark.parametrize("case", ["periodic", "adaptive_mixed", "no_cache",
+                                  "no_cache_periodic"])
+def test_device_walk_equals_host_walk(gpu_ctx, monkeypatch, case):
     """The device walk (default) and the host walk (SWH_HOST_WALK) make the
     same decisions: identical counts, and the same accelerations up to the
-    summation order of the sorted vs. task-ordered lists."""
-    g, cells, tops = ics.gravity_tree(clumpy_box(14, seed=21), 4, split_size=24)
-    pairs = ics.top_level_pairs(tops)
-    r_s = 1.25 / 32
-    G = params(periodic=True, theta=0.6, r_s_inv=1 / r_s, r_cut_min=0.1 * r_s,
-               r_cut_max=4.5 * r_s)
+    summation order of the sorted vs. task-ordered lists. Periodic with the
+    r_cut_max skip, the adaptive MAC over mixed activity (no box), and the
+    no-cache tasks of single-gpart cells with and without a box."""
+    g, cells, tops, pairs, G = walk_case(case)
     gd, gh = abi.copy_parts(g), abi.copy_parts(g)
     sd = run_gpu(gpu_ctx, gd, cells, tops, pairs, G)[0]
     monkeypatch.setenv("SWH_HOST_WALK", "1")
     sh = run_gpu(gpu_ctx, gh, cells, tops, pairs, G)[0]
     monkeypatch.delenv("SWH_HOST_WALK")
     sd.pop("ms"), sh.pop("ms")  # phase timings
-    assert sd == sh and sd["n_m2l"] > 0 and sd["n_skipped"] > 0
+    assert sd == sh and sd["n_m2l"] > 0 and sd["n_pp_tasks"] > 0
+    assert (sd["n_skipped"] > 0) == bool(G.periodic)
     compare(gd, gh, rel=1e-9)
+
+
+@pytest.mark.parametrize("case", ["no_cache", "no_cache_periodic"])
+def test_tree_of_single_gpart_cells_vs_oracle(gpu_ctx, case):
+    """split_size 1: every leaf holds one gpart, so every pair of the walk that
+    reaches a leaf is a no-cache task (runner_dopair_grav_pp_no_cache)."""
+    g, cells, tops, pairs, G = walk_case(case)
+    assert cells["count"][cells["split"] == 0].max() == 1
+    gg, go = abi.copy_parts(g), abi.copy_parts(g)
+    st = run_gpu(gpu_ctx, gg, cells, tops, pairs, G)[0]
+    so, _ = run_oracle(go, cells, tops, pairs, G)
+    assert [st["n_pp"], st["n_m2p"], st["n_m2l"], st["n_pp_tasks"], st["n_skipped"],
+            st["n_pp_truncated"]] == list(so)
+    assert (so[2], so[3], so[4]) == WALK_CASES[case][1]
+    compare(gg, go)
 
 
 def test_tree_truncated_pair_count(gpu_ctx):

@@ -2,7 +2,7 @@
 # Experimental build: libswifthip with swh_hydro.hip compiled under extra
 # defines (e.g. -DSWH_TILE_WPE=4), written to swift_subtask_dev_amd/_exp/<name>.so.
 # Load it with SWH_LIB_PATH=swift_subtask_dev_amd/_exp/<name>.so.
-# usage: tools/build_variant.sh <name> <defines...>   (SRC=swh_grav.hip for the gravity file)
+# usage: tools/build_variant.sh <name> <defines...>   (SRC=swh_grav.hip: batch P2P / M2P, SRC=swh_gwalk.hip: tree gravity)
 set -e
 name="$1"; shift
 src="${SRC:-swh_hydro.hip}"
