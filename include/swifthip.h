@@ -1264,6 +1264,75 @@ SWH_API swh_status swh_gspace_fof_groups(swh_gspace *g, int64_t *size, double *m
  * reads of the level counts), links, flatten, catalogue. -1 before any call. */
 SWH_API swh_status swh_gspace_fof_times(swh_gspace *g, float *ms);
 
+/* ------------------------------------------------------------------ */
+/* Matter power spectra of a gspace (added to ABI v15; purely          */
+/* additive): SWIFT's power_spectrum (src/power_spectrum.c) on the     */
+/* device. Per folding f the gparts of a type are folded into a box of */
+/* dim / fold_factor^f, assigned to an N^3 grid of plain mass with the */
+/* NGP, CIC or TSC window, transformed (hipFFT D2Z), and the modes     */
+/* inside the Nyquist sphere are deconvolved and summed per shell      */
+/* bin = (int)(sqrt(kk) + 0.5). Not covered: the electron-pressure     */
+/* spectra, the split neutrino ensembles and the delta-f weighting,    */
+/* spectra across ranks, the text files. Nothing here writes a record, */
+/* the tree, a multipole or the PM mesh's buffers, marks the tree      */
+/* stale or needs a tree.                                              */
+/* ------------------------------------------------------------------ */
+#define SWH_POWER_MAX_SPECTRA 8
+#define SWH_POWER_MAX_FOLDS 16
+typedef enum swh_power_type { /* enum power_type, by the reference's names */
+  SWH_POWER_MATTER = 0,   /* every gpart */
+  SWH_POWER_CDM = 1,      /* types 1 and 2 */
+  SWH_POWER_GAS = 2,      /* type 0 */
+  SWH_POWER_STARBH = 3,   /* types 4 and 5 */
+  SWH_POWER_NEUTRINO = 4  /* type 6, weight 1 */
+} swh_power_type;
+typedef struct swh_power_params {
+  int32_t N;            /* grid side, 2..1024, even or odd */
+  int32_t window_order; /* 1 NGP, 2 CIC, 3 TSC */
+  int32_t n_folds;      /* 1..SWH_POWER_MAX_FOLDS */
+  int32_t fold_factor;  /* >= 1 */
+  int32_t n_spectra;    /* 1..SWH_POWER_MAX_SPECTRA pairs (type1[s], type2[s]) */
+  int32_t type1[SWH_POWER_MAX_SPECTRA];
+  int32_t type2[SWH_POWER_MAX_SPECTRA];
+  int32_t reserved;
+  double dim[3];        /* the box: equal on the three axes (power_spectrum.c:1050) */
+} swh_power_params;
+/* Queues the whole calculation on the gspace's stream, the foldings one after
+ * the other without a host wait, and one copy of the results to pinned memory
+ * at the end. Each distinct type's grid is assigned and transformed once per
+ * folding however many pairs name it. Inhibited gparts contribute nothing; nor
+ * does a gpart one of whose coordinates is not finite (or so large that a
+ * double no longer resolves the box): those are counted in n_nonfinite. The
+ * grids take global fp64 atomics, so general masses can round differently from
+ * call to call; the shell sums and the shot noise use no floating-point atomic
+ * and give the same bits for the same grid. The type is read through
+ * swh_gspace_set_step_layout: without it only SWH_POWER_MATTER can be asked
+ * (every gpart counts), any other type is SWH_ERR_STATE. SWH_ERR_STATE before
+ * swh_gspace_upload; SWH_ERR_ARG for any parameter out of range, an unknown
+ * type or unequal dim; SWH_ERR_HIP (with a message) if hipFFT fails. An empty
+ * set gives zero sums and zero gpart counts. */
+SWH_API swh_status swh_gspace_power_spectrum(swh_gspace *g, const swh_power_params *P);
+/* Waits for the last swh_gspace_power_spectrum; SWH_ERR_STATE if there was
+ * none, SWH_ERR_ARG unless n_spectra, n_folds and n_bins = N / 2 + 1 are that
+ * call's. Per spectrum s and folding f, at (s * n_folds + f) * n_bins:
+ * modecounts (the sum of mult per bin) and powersum (the sum of mult W^2
+ * (Re1 Re2 + Im1 Im2) of the transforms of plain mass: multiply by
+ * invcellmean_1 invcellmean_2 volume / N^6 for the reference's). Per spectrum:
+ * shot_sum (sum of q1 q2 over the gparts in both fields, 0 unless a field is
+ * matter or the two are the same), n_contributing[2 s + {0, 1}] (gparts in
+ * field 1, in field 2) and n_nonfinite (gparts of either field left out for
+ * their position). Any pointer may be NULL. */
+SWH_API swh_status swh_gspace_power_spectrum_result(swh_gspace *g, int32_t n_spectra,
+                                                    int32_t n_folds, int32_t n_bins,
+                                                    int64_t *modecounts, double *powersum,
+                                                    double *shot_sum, int64_t *n_contributing,
+                                                    int64_t *n_nonfinite);
+/* Device time of the stages of the last swh_gspace_power_spectrum (ms, HIP
+ * events on the gspace's stream, summed over foldings, types and pairs; waits
+ * for them): ms[0..4) = assignment, transforms, binning, shot noise.
+ * SWH_ERR_STATE before any call. */
+SWH_API swh_status swh_gspace_power_spectrum_times(swh_gspace *g, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -533,6 +533,34 @@ class FofResult(C.Structure):
         return {n: int(getattr(self, n)) for n in FOF_RESULT_FIELDS}
 
 
+POWER_MAX_SPECTRA = 8  # SWH_POWER_MAX_SPECTRA
+POWER_MAX_FOLDS = 16   # SWH_POWER_MAX_FOLDS
+# swh_power_type, by the reference's names (get_powtype_filename)
+POWER_TYPES = {"matter": 0, "cdm": 1, "gas": 2, "starBH": 3, "neutrino": 4}
+POWER_STAGES = ("assignment", "transforms", "binning", "shot_noise")
+
+
+class PowerParams(C.Structure):
+    """swh_power_params: the power spectra of a gspace. spectra: pairs of
+    POWER_TYPES codes."""
+
+    _fields_ = [("N", C.c_int32), ("window_order", C.c_int32), ("n_folds", C.c_int32),
+                ("fold_factor", C.c_int32), ("n_spectra", C.c_int32),
+                ("type1", C.c_int32 * POWER_MAX_SPECTRA), ("type2", C.c_int32 * POWER_MAX_SPECTRA),
+                ("reserved", C.c_int32), ("dim", C.c_double * 3)]
+
+    def __init__(self, N=256, window_order=3, n_folds=1, fold_factor=4, spectra=((0, 0),),
+                 dim=(1.0, 1.0, 1.0)):
+        spectra = list(spectra)
+        if len(spectra) > POWER_MAX_SPECTRA:
+            raise ValueError(f"at most {POWER_MAX_SPECTRA} spectra in one call")
+        t1 = [int(a) for a, _ in spectra] + [0] * (POWER_MAX_SPECTRA - len(spectra))
+        t2 = [int(b) for _, b in spectra] + [0] * (POWER_MAX_SPECTRA - len(spectra))
+        super().__init__(int(N), int(window_order), int(n_folds), int(fold_factor), len(spectra),
+                         (C.c_int32 * POWER_MAX_SPECTRA)(*t1),
+                         (C.c_int32 * POWER_MAX_SPECTRA)(*t2), 0, (C.c_double * 3)(*dim))
+
+
 class GCell(C.Structure):
     """swh_gcell: a tree cell's gpart range, progeny and geometry."""
 

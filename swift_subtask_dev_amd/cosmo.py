@@ -307,6 +307,44 @@ def fof_linking_length(ratio: float, dm_mass: float, cosmo: Cosmology, with_hydr
     return float(ratio * np.cbrt(dm_mass / (omega * rho_crit0)))
 
 
+def power_cuts(grid_side_length: int, window_order: int, num_folds: int, fold_factor: int) -> dict:
+    """The k-cuts of the combined spectrum (power_spectrum.c:1024-1029) and
+    power_init's test of them (:1277-1283): kcutleft, kcutright, numtot,
+    admissible. csrc/swh_power.h power_cuts states the same."""
+    kcutn = 90 if window_order >= 3 else 70
+    kcutleft = int(grid_side_length / 256.0 * kcutn)
+    kcutright = int(grid_side_length / 256.0 * float(kcutn) / fold_factor)
+    return {"kcutleft": kcutleft, "kcutright": kcutright,
+            "numtot": kcutleft + (num_folds - 1) * (kcutleft - kcutright + 1),
+            "admissible": not (kcutright < 10 or (kcutleft - kcutright) < 30)}
+
+
+def power_combine(k: np.ndarray, P: np.ndarray, shot_noise: float, grid_side_length: int,
+                  window_order: int = 3, fold_factor: int = 4) -> dict:
+    """The combined spectrum from the per-fold arrays (foldings x N/2+1, entry
+    j: bin j), as power_spectrum.c:1171-1190: the first kcutleft bins of
+    folding 0, then bins kcutright+1 .. kcutleft+1 of every further folding.
+    Returns the reference's output columns (:1210-1213): `k`, `P` with the
+    shot noise subtracted, and `shot_noise`. ValueError where power_init would
+    error()."""
+    k, P = np.asarray(k, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    if k.ndim != 2 or k.shape != P.shape or k.shape[1] != grid_side_length // 2 + 1:
+        raise ValueError("power_combine: k and P are foldings x (N / 2 + 1)")
+    c = power_cuts(grid_side_length, window_order, k.shape[0], fold_factor)
+    if not c["admissible"]:
+        raise ValueError("Combination of power grid size and fold factor do not allow for "
+                         "enough overlap between foldings!")
+    left, right = c["kcutleft"], c["kcutright"]
+    ks, ps = [k[0, 1:left + 1]], [P[0, 1:left + 1]]
+    for f in range(1, k.shape[0]):
+        ks.append(k[f, right + 1:left + 2])
+        ps.append(P[f, right + 1:left + 2])
+    kcomb, pcomb = np.concatenate(ks), np.concatenate(ps)
+    assert len(kcomb) == c["numtot"]
+    return {"k": kcomb, "P": pcomb - shot_noise, "shot_noise": np.full(len(kcomb), shot_noise),
+            **c}
+
+
 def first_dm_mass(gparts: np.ndarray) -> float:
     """The mass of the first dark-matter gpart (type 1) that is neither
     inhibited nor not yet created (fof.c:264-274); 0 when there is none."""

@@ -1312,6 +1312,7 @@ swh_status swh_gspace_destroy(swh_gspace* g) {
   gstep_release(g);
   couple_release(g);
   fof_release(g);
+  power_release(g);
   (void)hipStreamDestroy(g->stream);
   delete g;
   return SWH_OK;

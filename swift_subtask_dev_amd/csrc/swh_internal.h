@@ -230,6 +230,10 @@ struct RmsState {
 // outputs and the pinned copy of its counters.
 struct FofState;
 
+// The power spectra of a gspace (swh_power.hip): its own grids, hipFFT plans
+// and tables per N, the partial sums, the pinned copy of the results.
+struct PowerState;
+
 // Device copy of the AoS layout (offsets), passed by value to kernels.
 struct Layout {
   int stride;
@@ -496,10 +500,12 @@ struct swh_gspace {
   swh::StatsState stats;  // swh_gspace_statistics / _sync_velocities (swh_stats.hip)
   swh::RmsState rms;      // swh_gspace_displacement_sums (swh_rms.hip)
   swh::FofState* fof = nullptr;  // swh_gspace_fof (swh_fof.hip), made by the first call
+  swh::PowerState* power = nullptr;  // swh_gspace_power_spectrum (swh_power.hip), likewise
 };
 
 namespace swh {
 void fof_release(swh_gspace* g);   // swh_fof.hip: the search's buffers, event and timer
+void power_release(swh_gspace* g);  // swh_power.hip: the spectra's grids, plans, events
 void mesh_release(swh_gspace* g);  // swh_mesh.hip: mesh buffers and hipFFT plans
 void gtree_release(swh_gspace* g);  // swh_gtree.hip: the tree build's scratch and events
 void gstep_release(swh_gspace* g);  // swh_gkick.hip: the step record and the stage timer

@@ -272,6 +272,7 @@ class _GravityDriver:
         self.dt_max_rms = float(np.finfo(np.float32).max)
         self._rms_pending = False
         self.groups = None  # (ti_current, the result of the last find_groups)
+        self.power_spectra = None  # (ti_current, the result of the last power_spectrum)
         self._tree_fresh = False  # the installed tree is of the gparts as they are
         self._dm_mass = 0.0  # the first existing dark-matter gpart's (fof.c:264-274)
 
@@ -504,6 +505,40 @@ class _GravityDriver:
         res = self.gs.fof(F, upload_order=upload_order)
         res["linking_length"] = float(linking_length)
         self.groups = (self.ti_current, res)
+        return res
+
+    # -- matter power spectra ---------------------------------------------
+    def power_spectrum(self, requested=(("matter", "matter"),), grid_side_length: int = 256,
+                       num_folds: int = 3, fold_factor: int = 4, window_order: int = 3,
+                       mean_density: float = None) -> dict:
+        """The power spectra of the gparts at ti_current (SWIFT's --power,
+        power_spectrum.c), on the device: valid wherever collect_statistics
+        and find_groups are, after the drift; no tree is needed. The defaults
+        are the reference's (:50-52). mean_density: the mean comoving matter
+        density; by default (Omega_cdm + Omega_b) 3 H0^2 / (8 pi G) of the
+        driver's cosmology (:911-914), so without a cosmology it must be given.
+        Nothing of the run is changed: a run with power_spectrum equals one
+        without bit for bit. Returns, per requested pair, GravSpace.
+        power_spectrum's dict plus `combined` (cosmo.power_combine: raises
+        ValueError where power_init would refuse the grid and the fold factor),
+        and keeps (ti_current, dict) in .power_spectra."""
+        if mean_density is None:
+            if self.cosmology is None:
+                raise ValueError("power_spectrum needs mean_density= without a cosmology")
+            cm = self.cosmology
+            rho_crit0 = 3.0 * cm.H0 * cm.H0 / (8.0 * np.pi * self.const_G)
+            mean_density = (cm.Omega_cdm + cm.Omega_b) * rho_crit0
+        cuts = cosmo_mod.power_cuts(grid_side_length, window_order, num_folds, fold_factor)
+        if not cuts["admissible"]:
+            raise ValueError("Combination of power grid size and fold factor do not allow for "
+                             "enough overlap between foldings!")
+        res = self.gs.power_spectrum(requested, grid_side_length, num_folds, fold_factor,
+                                     window_order, self.box, float(mean_density))
+        for spec in res.values():
+            spec["combined"] = cosmo_mod.power_combine(spec["k"], spec["P"], spec["shot_noise"],
+                                                       grid_side_length, window_order, fold_factor)
+            spec["mean_density"] = float(mean_density)
+        self.power_spectra = (self.ti_current, res)
         return res
 
 

@@ -76,6 +76,8 @@ HIP_SYMBOLS = [
     "swh_dt_max_rms_displacement",
     "swh_gspace_fof", "swh_gspace_fof_result", "swh_gspace_fof_roots",
     "swh_gspace_fof_group_ids", "swh_gspace_fof_groups", "swh_gspace_fof_times",
+    "swh_gspace_power_spectrum", "swh_gspace_power_spectrum_result",
+    "swh_gspace_power_spectrum_times",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -262,6 +264,9 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
         "swh_gspace_fof_group_ids": (C.c_int, [vp, vp]),
         "swh_gspace_fof_groups": (C.c_int, [vp, vp, vp, vp, vp, i32]),
         "swh_gspace_fof_times": (C.c_int, [vp, P(C.c_float)]),
+        "swh_gspace_power_spectrum": (C.c_int, [vp, P(abi.PowerParams)]),
+        "swh_gspace_power_spectrum_result": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "swh_gspace_power_spectrum_times": (C.c_int, [vp, P(C.c_float)]),
     }
     missing = [name for name in sigs if not hasattr(lib, name)]
     if missing:
@@ -1104,6 +1109,83 @@ class GravSpace:
         ms = (C.c_float * 4)()
         _check(self._lib.swh_gspace_fof_times(self.handle, ms), "gspace_fof_times", self._lib)
         return dict(zip(("leaf_pairs", "links", "flatten", "catalogue"), map(float, ms)))
+
+    # ---- matter power spectra (swh_power.hip) ------------------------------
+    def power_spectrum_enqueue(self, P: abi.PowerParams):
+        """Queue every folding of every requested pair on the gspace's stream."""
+        _check(self._lib.swh_gspace_power_spectrum(self.handle, C.byref(P)),
+               "gspace_power_spectrum", self._lib)
+        self._power = (int(P.n_spectra), int(P.n_folds), int(P.N) // 2 + 1)
+
+    def power_spectrum_result(self) -> dict:
+        """Wait for the last power_spectrum_enqueue; its raw sums: modecounts
+        and powersum (spectra x foldings x N/2+1), shot_sum, n_contributing
+        (spectra x 2) and n_nonfinite per spectrum."""
+        ns, nf, nb = getattr(self, "_power", (0, 0, 0))
+        out = {"modecounts": np.zeros((ns, nf, nb), dtype=np.int64),
+               "powersum": np.zeros((ns, nf, nb)), "shot_sum": np.zeros(ns),
+               "n_contributing": np.zeros((ns, 2), dtype=np.int64),
+               "n_nonfinite": np.zeros(ns, dtype=np.int64)}
+        _check(self._lib.swh_gspace_power_spectrum_result(
+            self.handle, ns, nf, nb, _ptr(out["modecounts"]), _ptr(out["powersum"]),
+            _ptr(out["shot_sum"]), _ptr(out["n_contributing"]), _ptr(out["n_nonfinite"])),
+            "gspace_power_spectrum_result", self._lib)
+        return out
+
+    def power_spectrum(self, requested=(("matter", "matter"),), grid_side_length: int = 256,
+                       num_folds: int = 1, fold_factor: int = 4, window_order: int = 3,
+                       box: float = 1.0, mean_density: float = 1.0) -> dict:
+        """The power spectra of the gparts as they are (SWIFT's --power). Per
+        requested pair of abi.POWER_TYPES names a dict with, per folding f,
+        `k` (j 2 pi / (box / fold_factor^f)), `P` (powersum / modecounts *
+        volume / N^6 * invcellmean_1 invcellmean_2, the shot noise included;
+        0 in the empty bin 0), `modecounts` and `powersum`, and `shot_noise`,
+        `n_contributing` and `n_nonfinite`. mean_density: the mean matter
+        density both fields are contrasts of (power_spectrum.c:911-922)."""
+        pairs = []
+        for a, b in requested:
+            if a not in abi.POWER_TYPES or b not in abi.POWER_TYPES:
+                raise ValueError(f"unknown power spectrum type in {(a, b)!r}: "
+                                 f"{sorted(abi.POWER_TYPES)}")
+            pairs.append((abi.POWER_TYPES[a], abi.POWER_TYPES[b]))
+        if not mean_density > 0.0:
+            raise ValueError("power_spectrum needs mean_density > 0")
+        N = int(grid_side_length)
+        self.power_spectrum_enqueue(abi.PowerParams(N, window_order, num_folds, fold_factor,
+                                                    pairs, (box,) * 3))
+        raw = self.power_spectrum_result()
+        volume = box * box * box
+        n3 = float(N * N * N)
+        invcellmean = n3 / (mean_density * volume)
+        volfac = (volume / n3) / n3
+        dim = box
+        k = np.zeros((int(num_folds), N // 2 + 1))
+        for f in range(int(num_folds)):
+            k[f] = np.arange(N // 2 + 1) * (2 * np.pi / dim)
+            dim /= fold_factor
+        res = {}
+        for s, names in enumerate(requested):
+            cnt, S = raw["modecounts"][s], raw["powersum"][s]
+            Pk = np.zeros_like(S)
+            np.divide(S, cnt, out=Pk, where=cnt > 0)
+            Pk = Pk * volfac * (invcellmean * invcellmean)
+            shot = float(raw["shot_sum"][s]) / volume
+            shot /= mean_density
+            shot /= mean_density
+            res[tuple(names)] = {
+                "k": k.copy(), "P": Pk, "modecounts": cnt, "powersum": S, "shot_noise": shot,
+                "shot_sum": float(raw["shot_sum"][s]),
+                "n_contributing": tuple(int(v) for v in raw["n_contributing"][s]),
+                "n_nonfinite": int(raw["n_nonfinite"][s])}
+        return res
+
+    def power_spectrum_ms(self) -> dict:
+        """HIP-event times (ms) of the stages of the last power spectrum call,
+        summed over foldings, types and pairs."""
+        ms = (C.c_float * 4)()
+        _check(self._lib.swh_gspace_power_spectrum_times(self.handle, ms),
+               "gspace_power_spectrum_times", self._lib)
+        return dict(zip(abi.POWER_STAGES, map(float, ms)))
 
     def sync(self):
         _check(self._lib.swh_gspace_sync(self.handle), "gspace_sync", self._lib)
