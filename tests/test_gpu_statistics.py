@@ -501,6 +501,11 @@ def test_hydro_integrator_statistics(gpu_ctx):
     mv = (parts["mass"][:, None] * parts["v"]).astype(D)
     assert np.all(np.abs(e0["mom"] - mv.sum(axis=0)) <= RS.bound(N, np.abs(mv).sum(axis=0)) * 2)
     assert e0["n_counted"] == N and e0["E_pot_self"] == 0 and e0["dm_mass"] == 0
+    # (for the record only: this run has several time bins, so inactive partners
+    # break the pairwise cancellation. The one-bin run is held to momentum
+    # conservation and to the CPU route's second-order energy error in
+    # test_gpu_hydro_invariants.py::test_run_momentum_is_constant and
+    # ::test_run_energy_second_order.)
     drift = [abs(s["E_tot"] - e0["E_tot"]) / abs(e0["E_tot"]) for _, s in integ.statistics]
     print("\nhydro E_tot drift per step", drift)
 
