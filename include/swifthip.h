@@ -1333,6 +1333,87 @@ SWH_API swh_status swh_gspace_power_spectrum_result(swh_gspace *g, int32_t n_spe
  * SWH_ERR_STATE before any call. */
 SWH_API swh_status swh_gspace_power_spectrum_times(swh_gspace *g, float *ms);
 
+/* ------------------------------------------------------------------ */
+/* Lightcone particle crossings of a gspace (added to ABI v15; purely  */
+/* additive): SWIFT's lightcone_check_particle_crosses                 */
+/* (src/lightcone/lightcone_crossing.h) for one lightcone and one      */
+/* drift, on the device and before that drift. Every live gpart whose  */
+/* type is used is tested against every periodic replication of the    */
+/* list; a copy crosses when its r2 at the start of the drift is at    */
+/* most R_start^2 and its r2 at the end at least R_end^2, all in fp64  */
+/* in the reference's operation order without fused multiply-adds.     */
+/* Not covered: the HEALPix maps, the gas, star, sink and black-hole   */
+/* property fields and their output filters, the HDF5 writer,          */
+/* lightcones across ranks. Nothing here writes a record, the tree or  */
+/* a multipole, marks the tree stale or needs a tree.                  */
+/* ------------------------------------------------------------------ */
+#define SWH_LIGHTCONE_TYPES 7 /* swift_type_count */
+typedef struct swh_lightcone_replication { /* struct replication */
+  double rmin2, rmax2; /* squares of the distance range of the copy of the box */
+  double coord[3];     /* what the copy adds to a position */
+} swh_lightcone_replication;
+typedef struct swh_lightcone_params {
+  double observer[3];
+  double R_start, R_end; /* comoving distance at the drift's start and end: R_end <= R_start */
+  double dt_drift;       /* the drift's factor on v_full */
+  double dim[3];         /* the box: periodic and equal on the three axes */
+  int32_t periodic;
+  int32_t n_replications;
+  const swh_lightcone_replication *replications; /* host memory, ascending rmin2 */
+  int32_t use_type[SWH_LIGHTCONE_TYPES];
+  int32_t no_cull;       /* non-zero: every block meets every replication (for measurement) */
+  double r2_min[SWH_LIGHTCONE_TYPES]; /* a crossing is kept when r2_min <= r2_cross <= r2_max */
+  double r2_max[SWH_LIGHTCONE_TYPES];
+  int64_t capacity;      /* crossings the output buffer holds, >= 0 */
+} swh_lightcone_params;
+typedef struct swh_lightcone_record {
+  int64_t id_or_neg_offset;
+  int32_t gpart;       /* index in the current device order */
+  int32_t replication; /* index into the list given */
+  double f;            /* the fraction of the drift at which the copy crosses */
+  double x_cross[3];   /* relative to the observer */
+  float v_full[3];
+  float mass;
+  int32_t type;
+  int32_t reserved;
+} swh_lightcone_record;
+typedef struct swh_lightcone_result {
+  int64_t n_crossings;  /* crossings the type filter keeps: exact, whatever the capacity */
+  int64_t n_stored;     /* of those, records in the buffer: all of them when n_slots <= capacity */
+  int64_t n_slots;      /* the capacity that stores every crossing (slots are reserved before the
+                           type filter's r2 range is applied, so n_slots >= n_crossings) */
+  int64_t n_bad_f;      /* crossings with f outside [-1e-5, 1 + 1e-5]: the reference's error() */
+  int64_t n_pair_tests; /* (gpart, replication) pairs that reached the particle tests */
+  int64_t n_tile_tests; /* (block, replication) pairs looked at by the cull */
+  int64_t n_tile_kept;  /* of those, pairs handed to the lanes */
+} swh_lightcone_result;
+/* Only enqueues on the gspace's stream: the replication list is copied, every
+ * block of 256 gparts culls the list against the bounding box of its gparts
+ * (compact after swh_gspace_build_tree), its lanes test what is left and append
+ * their crossings through one counter update per wave and 64 replications, and
+ * the stored records are sorted by (gpart, replication): the same state gives
+ * the same bytes on every call. When n_crossings > n_stored the stored records
+ * are some of them; call again with capacity >= n_slots before the drift (the
+ * pass changes nothing). Inhibited gparts are skipped, as the drift
+ * skips them; so is a gpart whose type is outside [0, SWH_LIGHTCONE_TYPES) or
+ * not used. SWH_ERR_STATE before swh_gspace_upload or
+ * swh_gspace_set_step_layout; SWH_ERR_ARG for a non-periodic or non-cubic box,
+ * R_end > R_start, a negative distance, a list not in ascending rmin2, a
+ * negative capacity or count, or any parameter that is not finite (r2_max may
+ * be +infinity). An empty set or an empty list queues nothing and gives zero
+ * counts. */
+SWH_API swh_status swh_gspace_lightcone_crossings(swh_gspace *g, const swh_lightcone_params *P);
+/* Waits for the last swh_gspace_lightcone_crossings; SWH_ERR_STATE if there
+ * was none (so the call below). */
+SWH_API swh_status swh_gspace_lightcone_result(swh_gspace *g, swh_lightcone_result *out);
+/* The first n sorted records; SWH_ERR_ARG unless 0 <= n <= n_stored. */
+SWH_API swh_status swh_gspace_lightcone_records(swh_gspace *g, swh_lightcone_record *records,
+                                                int64_t n);
+/* Device time of the stages of the last swh_gspace_lightcone_crossings (ms, HIP
+ * events on the gspace's stream; waits for them): ms[0..2) = the pass (list
+ * copy, cull, tests, append), the sort. -1 before any call. */
+SWH_API swh_status swh_gspace_lightcone_times(swh_gspace *g, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -561,6 +561,60 @@ class PowerParams(C.Structure):
                          (C.c_int32 * POWER_MAX_SPECTRA)(*t2), 0, (C.c_double * 3)(*dim))
 
 
+LIGHTCONE_TYPES = 7  # SWH_LIGHTCONE_TYPES (swift_type_count)
+# swh_lightcone_replication (struct replication)
+LIGHTCONE_REP_DTYPE = np.dtype([("rmin2", "<f8"), ("rmax2", "<f8"), ("coord", "<f8", 3)])
+# swh_lightcone_record
+LIGHTCONE_RECORD_DTYPE = np.dtype({
+    "names": ["id_or_neg_offset", "gpart", "replication", "f", "x_cross", "v_full", "mass", "type"],
+    "formats": ["<i8", "<i4", "<i4", "<f8", ("<f8", 3), ("<f4", 3), "<f4", "<i4"],
+    "offsets": [0, 8, 12, 16, 24, 48, 60, 64], "itemsize": 72})
+LIGHTCONE_RESULT_FIELDS = ("n_crossings", "n_stored", "n_slots", "n_bad_f", "n_pair_tests",
+                           "n_tile_tests", "n_tile_kept")
+LIGHTCONE_STAGES = ("pass", "sort")
+
+
+class LightconeParams(C.Structure):
+    """swh_lightcone_params: one lightcone's crossing pass before one drift.
+    replications: a LIGHTCONE_REP_DTYPE array in ascending rmin2 (kept alive
+    by this object); use_types: the types that are tested; r2_range: {type:
+    (r2_min, r2_max)} for the types whose crossings are kept only inside it."""
+
+    _fields_ = [("observer", C.c_double * 3), ("R_start", C.c_double), ("R_end", C.c_double),
+                ("dt_drift", C.c_double), ("dim", C.c_double * 3), ("periodic", C.c_int32),
+                ("n_replications", C.c_int32), ("replications", C.c_void_p),
+                ("use_type", C.c_int32 * LIGHTCONE_TYPES), ("no_cull", C.c_int32),
+                ("r2_min", C.c_double * LIGHTCONE_TYPES), ("r2_max", C.c_double * LIGHTCONE_TYPES),
+                ("capacity", C.c_int64)]
+
+    def __init__(self, observer=(0.0, 0.0, 0.0), R_start=0.0, R_end=0.0, dt_drift=0.0,
+                 dim=(1.0, 1.0, 1.0), periodic=1, replications=None,
+                 use_types=tuple(range(LIGHTCONE_TYPES)), r2_range=None, capacity=0, no_cull=0):
+        reps = np.ascontiguousarray(
+            replications if replications is not None else np.zeros(0, LIGHTCONE_REP_DTYPE),
+            dtype=LIGHTCONE_REP_DTYPE)
+        self._reps = reps  # the pointer below is into it
+        use = [1 if t in tuple(use_types) else 0 for t in range(LIGHTCONE_TYPES)]
+        lo, hi = [0.0] * LIGHTCONE_TYPES, [float("inf")] * LIGHTCONE_TYPES
+        for t, (a, b) in (r2_range or {}).items():
+            lo[int(t)], hi[int(t)] = float(a), float(b)
+        super().__init__((C.c_double * 3)(*observer), float(R_start), float(R_end),
+                         float(dt_drift), (C.c_double * 3)(*dim), int(periodic), len(reps),
+                         reps.ctypes.data if len(reps) else None,
+                         (C.c_int32 * LIGHTCONE_TYPES)(*use), int(no_cull),
+                         (C.c_double * LIGHTCONE_TYPES)(*lo), (C.c_double * LIGHTCONE_TYPES)(*hi),
+                         int(capacity))
+
+
+class LightconeResult(C.Structure):
+    """swh_lightcone_result: the counts of the last pass."""
+
+    _fields_ = [(n, C.c_int64) for n in LIGHTCONE_RESULT_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in LIGHTCONE_RESULT_FIELDS}
+
+
 class GCell(C.Structure):
     """swh_gcell: a tree cell's gpart range, progeny and geometry."""
 

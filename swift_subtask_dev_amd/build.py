@@ -35,11 +35,12 @@ VARIANTS = {
 HIP_SOURCES = ["swh_api.hip", "swh_tasks.hip", "swh_space.hip", "swh_hydro.hip", "swh_grav.hip",
                "swh_mesh.hip", "swh_kick.hip", "swh_gtree.hip", "swh_gkick.hip", "swh_couple.hip",
                "swh_limiter.hip", "swh_stats.hip", "swh_rms.hip", "swh_fof.hip", "swh_gwalk.hip",
-               "swh_power.hip"]
+               "swh_power.hip", "swh_lightcone.hip"]
 HIP_HEADERS = ["swh_internal.h", "swh_physics.h", "swh_space.h", "swh_gather.h", "swh_wave.h",
                "swh_list.h", "swh_mpole.h", "swh_timeline.h", "swh_gstep.h", "swh_couple.h",
                "swh_limiter.h", "swh_steprec.h", "swh_stats.h", "swh_rms.h", "swh_fof.h",
-               "swh_grec.h", "swh_grav.h", "swh_gwalk.h", "swh_power.h"]
+               "swh_grec.h", "swh_grav.h", "swh_gwalk.h", "swh_power.h",
+               "swh_lightcone.h"]
 
 
 def _hipcc() -> str:

@@ -345,6 +345,127 @@ def power_combine(k: np.ndarray, P: np.ndarray, shot_noise: float, grid_side_len
             **c}
 
 
+# -- lightcones (src/lightcone/, cosmology.c:1315-1351) ------------------------
+_DIST_PANELS, _DIST_NODES = 8, 16
+
+
+def comoving_distance(cosmo: Cosmology, a, speed_of_light: float):
+    """cosmology_get_comoving_distance: c int_a^1 da' / (a'^2 H) = c int
+    dlog(a') / (a' H) from log a to 0. SWIFT interpolates a table of the
+    integral (cosmology.c:358-366, 750-790, 1315-1332); here it is the integral
+    itself, by a 16-point Gauss-Legendre rule on each of 8 equal panels in log a, as
+    the kick integrals are rules and not tables: one smooth function of a, the
+    same bits for the same a, scalar or array."""
+    scalar = np.ndim(a) == 0
+    x = np.log(np.atleast_1d(np.asarray(a, dtype=np.float64)))
+    xg, wg = np.polynomial.legendre.leggauss(_DIST_NODES)
+    h = (0.0 - x) / _DIST_PANELS                       # panel width per a
+    lo = x[:, None] + h[:, None] * np.arange(_DIST_PANELS)[None, :]
+    nodes = lo[:, :, None] + 0.5 * h[:, None, None] * (xg[None, None, :] + 1.0)
+    an = np.exp(nodes)
+    integrand = 1.0 / (an * cosmo.H(an))
+    panel = (0.5 * h[:, None, None] * wg[None, None, :] * integrand).sum(axis=2)
+    r = speed_of_light * panel.sum(axis=1)
+    return float(r[0]) if scalar else r
+
+
+def scale_factor_at_comoving_distance(cosmo: Cosmology, r, speed_of_light: float):
+    """cosmology_scale_factor_at_comoving_distance: the a with
+    comoving_distance(a) = r, by root finding on that function (SWIFT
+    interpolates a table of the inverse, cosmology.c:1340-1351): Newton
+    steps in log a (dR / dlog a = -c / (a H)) kept inside a bracket that every
+    evaluation narrows, bisection where a step leaves it, until |R(a) - r| <=
+    1e-12 R(a_begin). r: a scalar or an array in [0, R(a_begin)] (a little
+    beyond extrapolates to a < a_begin)."""
+    scalar = np.ndim(r) == 0
+    r = np.atleast_1d(np.asarray(r, dtype=np.float64))
+    c = float(speed_of_light)
+    bar = 1.0e-12 * comoving_distance(cosmo, cosmo.a_begin, c)
+    lo = np.full(r.shape, cosmo.log_a_begin - 1.0)   # R(lo) >= r
+    hi = np.zeros(r.shape)                           # R(hi) = 0 <= r
+    # a first guess from a coarse table
+    xt = np.linspace(cosmo.log_a_begin - 1.0, 0.0, 129)
+    rt = comoving_distance(cosmo, np.exp(xt), c)
+    x = np.interp(r, rt[::-1], xt[::-1])
+    todo = np.ones(r.shape, dtype=bool)
+    for _ in range(200):
+        k = np.flatnonzero(todo)
+        if len(k) == 0:
+            break
+        ak = np.exp(x[k])
+        d = comoving_distance(cosmo, ak, c) - r[k]
+        done = np.abs(d) <= bar
+        todo[k[done]] = False
+        k, ak, d = k[~done], ak[~done], d[~done]
+        lo[k] = np.where(d > 0.0, x[k], lo[k])       # still too far: a must grow
+        hi[k] = np.where(d < 0.0, x[k], hi[k])
+        xn = x[k] + d * ak * cosmo.H(ak) / c
+        inside = (xn > lo[k]) & (xn < hi[k])
+        x[k] = np.where(inside, xn, 0.5 * (lo[k] + hi[k]))
+    else:
+        raise RuntimeError("scale_factor_at_comoving_distance did not converge")
+    a = np.exp(x)
+    return float(a[0]) if scalar else a
+
+
+def lightcone_replications(box: float, observer, rmin: float, rmax: float,
+                           cell_width: float = 0.0) -> np.ndarray:
+    """replication_list_init (lightcone_replications.c:61-153): the periodic
+    copies of the box that overlap the distances [rmin, rmax] from the
+    observer, as an abi.LIGHTCONE_REP_DTYPE array. The copies are visited with
+    i outermost and k innermost and then sorted by rmin2; the reference's
+    qsort leaves the order of equal keys open, here they keep the order of the
+    visit (a stable sort). rmin2 and rmax2 are the squares by one
+    multiplication (the reference calls pow(., 2.0))."""
+    obs = np.asarray(observer, dtype=np.float64)
+    half = 0.5 * box
+    hw = 0.5 * cell_width
+    rep_min = np.floor((obs - rmax - hw) / box).astype(np.int64)
+    rep_max = np.floor((obs + rmax + hw) / box).astype(np.int64)
+    axes = [np.arange(rep_min[d], rep_max[d] + 1) for d in range(3)]
+    I, J, K = np.meshgrid(*axes, indexing="ij")
+    ijk = np.stack([I.ravel(), J.ravel(), K.ravel()], axis=1).astype(np.float64)
+    centre = box * ijk + half - obs[None, :]
+    dmin = np.abs(centre) - half - hw
+    dmin = np.where(dmin < 0.0, 0.0, dmin)
+    rep_rmin = np.sqrt(dmin[:, 0] * dmin[:, 0] + dmin[:, 1] * dmin[:, 1] + dmin[:, 2] * dmin[:, 2])
+    dmax = np.abs(centre) + half + hw
+    rep_rmax = np.sqrt(dmax[:, 0] * dmax[:, 0] + dmax[:, 1] * dmax[:, 1] + dmax[:, 2] * dmax[:, 2])
+    keep = ~((rep_rmax < rmin) | (rep_rmin > rmax))
+    out = np.zeros(int(keep.sum()), dtype=abi.LIGHTCONE_REP_DTYPE)
+    out["rmin2"] = rep_rmin[keep] * rep_rmin[keep]
+    out["rmax2"] = rep_rmax[keep] * rep_rmax[keep]
+    out["coord"] = ijk[keep] * box
+    return out[np.argsort(out["rmin2"], kind="stable")]
+
+
+def lightcone_shell(cosmo: Cosmology, ti_old: int, ti_current: int, observer, box: float,
+                    a_min: float, a_max: float, speed_of_light: float,
+                    cell_width: float = 0.0) -> dict:
+    """What one drift over [ti_old, ti_current] hands to the crossing test:
+    a_start, a_end and the comoving distances R_start, R_end there
+    (lightcone_crossing.h:83-92), and the replication list of
+    lightcone_prepare_for_step (lightcone.c:1295-1318) for the same interval:
+    the copies that overlap [R_end - (R_start - R_end), R_start], the inner
+    boundary layer allowing for what a particle with v < c moves, clipped at 0.
+    The list is empty when the step lies outside [a_min, a_max] (:1310; the
+    crossing test's own check, lightcone_crossing.h:131, is the same)."""
+    a_end = cosmo.a_begin * math.exp(ti_current * cosmo.time_base)
+    a_start = max(cosmo.a_begin * math.exp(ti_old * cosmo.time_base), cosmo.a_begin)
+    rmin = comoving_distance(cosmo, a_end, speed_of_light)
+    rmax = comoving_distance(cosmo, a_start, speed_of_light)
+    if rmin > rmax:
+        raise ValueError("Lightcone has rmin > rmax")
+    out = {"a_start": a_start, "a_end": a_end, "R_start": rmax, "R_end": rmin}
+    boundary = rmax - rmin
+    rmin = max(rmin - boundary, 0.0)
+    if a_end < a_min or a_start > a_max:
+        out["replications"] = np.zeros(0, dtype=abi.LIGHTCONE_REP_DTYPE)
+    else:
+        out["replications"] = lightcone_replications(box, observer, rmin, rmax, cell_width)
+    return out
+
+
 def first_dm_mass(gparts: np.ndarray) -> float:
     """The mass of the first dark-matter gpart (type 1) that is neither
     inhibited nor not yet created (fof.c:264-274); 0 when there is none."""

@@ -1313,6 +1313,7 @@ swh_status swh_gspace_destroy(swh_gspace* g) {
   couple_release(g);
   fof_release(g);
   power_release(g);
+  lightcone_release(g);
   (void)hipStreamDestroy(g->stream);
   delete g;
   return SWH_OK;

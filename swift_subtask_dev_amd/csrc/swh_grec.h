@@ -1,6 +1,7 @@
 // swh_grec.h — the gpart record of a gspace: the one place that knows its
 // fields. Every gspace kernel outside the gravity calls (the step, the
-// statistics, the displacement sums, the gas link, the halo finder) takes its
+// statistics, the displacement sums, the gas link, the halo finder, the
+// lightcone pass) takes its
 // offsets, its checks and its loads and stores from here.
 //
 //   GRecLayout      the stride and every offset such a kernel uses, by value
@@ -95,6 +96,8 @@ constexpr unsigned kNeedStats = GF_X | GF_V_FULL | GF_A_GRAV | GF_A_GRAV_MESH | 
 constexpr unsigned kNeedRms = GF_V_FULL | GF_MASS | GF_TIME_BIN | GF_TYPE;
 constexpr unsigned kNeedLink = GF_X | GF_V_FULL | GF_A_GRAV | GF_A_GRAV_MESH | GF_TIME_BIN | GF_TYPE;
 constexpr unsigned kNeedFof = GF_X | GF_MASS | GF_TIME_BIN;  // and GF_TYPE with a step layout
+// (and GF_ID for the check: the kernel reads id_or_neg_offset as swh_couple.h does)
+constexpr unsigned kNeedLightcone = GF_X | GF_V_FULL | GF_MASS | GF_TIME_BIN | GF_TYPE;
 
 // Every field of `need` lies inside the record, aligned to its type (an
 // uploaded stride is a positive multiple of 8: make_glayout). Returns NULL, or

@@ -234,6 +234,10 @@ struct FofState;
 // and tables per N, the partial sums, the pinned copy of the results.
 struct PowerState;
 
+// The lightcone pass of a gspace (swh_lightcone.hip): the replication list,
+// the two record buffers, the sort's scratch, the pinned copy of the counters.
+struct LightconeState;
+
 // Device copy of the AoS layout (offsets), passed by value to kernels.
 struct Layout {
   int stride;
@@ -501,11 +505,13 @@ struct swh_gspace {
   swh::RmsState rms;      // swh_gspace_displacement_sums (swh_rms.hip)
   swh::FofState* fof = nullptr;  // swh_gspace_fof (swh_fof.hip), made by the first call
   swh::PowerState* power = nullptr;  // swh_gspace_power_spectrum (swh_power.hip), likewise
+  swh::LightconeState* lightcone = nullptr;  // swh_gspace_lightcone_crossings, likewise
 };
 
 namespace swh {
 void fof_release(swh_gspace* g);   // swh_fof.hip: the search's buffers, event and timer
 void power_release(swh_gspace* g);  // swh_power.hip: the spectra's grids, plans, events
+void lightcone_release(swh_gspace* g);  // swh_lightcone.hip: the pass's buffers, event, timer
 void mesh_release(swh_gspace* g);  // swh_mesh.hip: mesh buffers and hipFFT plans
 void gtree_release(swh_gspace* g);  // swh_gtree.hip: the tree build's scratch and events
 void gstep_release(swh_gspace* g);  // swh_gkick.hip: the step record and the stage timer

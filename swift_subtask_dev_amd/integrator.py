@@ -48,6 +48,12 @@ from . import abi, cosmo as cosmo_mod, ics, lib
 
 MAX_NR_TIMESTEPS = 1 << (abi.NUM_TIME_BINS + 1)
 
+# a lightcone crossing as the drivers keep it: the device's record, the scale
+# factor at which the copy crosses and vel = v_full / a_cross
+LIGHTCONE_DTYPE = np.dtype([(n, abi.LIGHTCONE_RECORD_DTYPE.fields[n][0])
+                            for n in abi.LIGHTCONE_RECORD_DTYPE.names]
+                           + [("a_cross", "<f8"), ("vel", "<f8", 3)])
+
 
 def get_max_active_bin(ti: int) -> int:
     """timeline.h:145-154: the largest bin whose steps end at ti."""
@@ -275,6 +281,7 @@ class _GravityDriver:
         self.power_spectra = None  # (ti_current, the result of the last power_spectrum)
         self._tree_fresh = False  # the installed tree is of the gparts as they are
         self._dm_mass = 0.0  # the first existing dark-matter gpart's (fof.c:264-274)
+        self.lightcones = []  # add_lightcone: the registered lightcones and their crossings
 
     # -- cosmological factors ---------------------------------------------
     def _softening_params(self, a: float) -> abi.GSofteningParams:
@@ -328,9 +335,91 @@ class _GravityDriver:
             return dt
         cm = self.cosmology
         dt = cosmo_mod._kick_integral(cm, ti_old, ti_new, 2.0) if ti_new > ti_old else 0.0
+        if ti_new > ti_old and self.lightcones:
+            self._lightcone_passes(ti_old, ti_new, dt)
         S = self._softening_params(cm.scale_factor(ti_new))
         self.gs.drift(dt, self.periodic, dim, softening=S)
         return dt
+
+    # -- lightcones ---------------------------------------------------------
+    def add_lightcone(self, observer, speed_of_light: float, z_range=None, a_range=None,
+                      use_types=tuple(range(abi.LIGHTCONE_TYPES)), z_range_for_type=None) -> int:
+        """Register a lightcone (src/lightcone/): from the next drift on, the
+        gparts' crossings of the past light cone of `observer` are found on the
+        device immediately before every gpart drift, with that drift's ti_old,
+        ti_current and dt_drift, and appended to .lightcones[i]["steps"] as
+        (ti_old, ti_current, LIGHTCONE_DTYPE array sorted by (gpart,
+        replication)): a_cross from the inverse comoving distance at |x_cross|,
+        vel = v_full / a_cross as lightcone_store_dark_matter does. May be
+        called more than once; one pass per lightcone. z_range or a_range: the
+        lightcone's extent (steps outside it get the empty replication list);
+        use_types: the gpart types that are tested; z_range_for_type: {type:
+        (z_min, z_max)}, crossings of that type are kept only at those
+        redshifts (r2_min_for_type / r2_max_for_type). In a CoupledIntegrator
+        the gas gparts are tested like every other type: at that point their x
+        and v_full are the gas's pre-drift values (x pushed after the last
+        drift, v_full after the last kick1). Nothing of the run is changed: a
+        run with lightcones equals one without bit for bit. Returns i."""
+        if self.cosmology is None:
+            raise ValueError("add_lightcone needs a cosmology (the comoving distance of a step)")
+        if not self.periodic:
+            raise ValueError("add_lightcone needs a periodic box")
+        if (z_range is None) == (a_range is None):
+            raise ValueError("give z_range or a_range")
+        if a_range is None:
+            z_lo, z_hi = sorted(float(z) for z in z_range)
+            a_range = (1.0 / (1.0 + z_hi), 1.0 / (1.0 + z_lo))
+        a_min, a_max = sorted(float(a) for a in a_range)
+        c = float(speed_of_light)
+        if not (c > 0.0 and np.isfinite(c)):
+            raise ValueError("speed_of_light must be positive and finite")
+        r2 = {}
+        for t, (z0, z1) in (z_range_for_type or {}).items():
+            z0, z1 = sorted((float(z0), float(z1)))
+            r_lo = cosmo_mod.comoving_distance(self.cosmology, 1.0 / (1.0 + z0), c)
+            r_hi = cosmo_mod.comoving_distance(self.cosmology, 1.0 / (1.0 + z1), c)
+            r2[int(t)] = (r_lo * r_lo, r_hi * r_hi)
+        self.lightcones.append({"observer": tuple(float(o) for o in observer), "a_min": a_min,
+                                "a_max": a_max, "speed_of_light": c,
+                                "use_types": tuple(int(t) for t in use_types), "r2_range": r2,
+                                "capacity": 0, "steps": [], "n_crossings": 0, "passes": 0})
+        return len(self.lightcones) - 1
+
+    def _lightcone_passes(self, ti_old: int, ti_new: int, dt_drift: float):
+        """Every registered lightcone's pass over the gparts as they are, for
+        the drift that follows. The pass writes nothing, so where its buffer
+        was too small it simply runs again (GravSpace.lightcone_crossings)."""
+        n = int(getattr(self.gs, "_n", 0))
+        for i, lc in enumerate(self.lightcones):
+            c = lc["speed_of_light"]
+            sh = cosmo_mod.lightcone_shell(self.cosmology, ti_old, ti_new, lc["observer"],
+                                           self.box, lc["a_min"], lc["a_max"], c)
+            reps = sh["replications"]
+            if len(reps) == 0 or n == 0:
+                lc["steps"].append((ti_old, ti_new, np.zeros(0, dtype=LIGHTCONE_DTYPE)))
+                continue
+            if lc["capacity"] == 0:  # a static, uniform box's share of the shell, and half again
+                shell = 4.0 / 3.0 * np.pi * (sh["R_start"] ** 3 - sh["R_end"] ** 3)
+                lc["capacity"] = int(1.5 * n * shell / self.box ** 3) + 4096
+            P = abi.LightconeParams(lc["observer"], sh["R_start"], sh["R_end"], dt_drift,
+                                    (self.box,) * 3, 1, reps, lc["use_types"], lc["r2_range"],
+                                    lc["capacity"])
+            rec, res = self.gs.lightcone_crossings(P)
+            lc["capacity"] = max(lc["capacity"], int(P.capacity))
+            lc["passes"] += res["passes"]
+            if res["n_bad_f"] > 0:
+                raise RuntimeError(f"lightcone {i}: {res['n_bad_f']} particles interpolated "
+                                   f"outside the time step [{ti_old}, {ti_new}]")
+            out = np.zeros(len(rec), dtype=LIGHTCONE_DTYPE)
+            for name in abi.LIGHTCONE_RECORD_DTYPE.names:
+                out[name] = rec[name]
+            x = rec["x_cross"]
+            r = np.sqrt(x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1] + x[:, 2] * x[:, 2])
+            out["a_cross"] = cosmo_mod.scale_factor_at_comoving_distance(self.cosmology, r, c) \
+                if len(rec) else 0.0
+            out["vel"] = rec["v_full"].astype(np.float64) / out["a_cross"][:, None]
+            lc["steps"].append((ti_old, ti_new, out))
+            lc["n_crossings"] += len(out)
 
     def _start_cosmology(self):
         """init_step, after the upload: every gpart gets the softening at

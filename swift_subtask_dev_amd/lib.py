@@ -78,6 +78,8 @@ HIP_SYMBOLS = [
     "swh_gspace_fof_group_ids", "swh_gspace_fof_groups", "swh_gspace_fof_times",
     "swh_gspace_power_spectrum", "swh_gspace_power_spectrum_result",
     "swh_gspace_power_spectrum_times",
+    "swh_gspace_lightcone_crossings", "swh_gspace_lightcone_result",
+    "swh_gspace_lightcone_records", "swh_gspace_lightcone_times",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -267,6 +269,10 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
         "swh_gspace_power_spectrum": (C.c_int, [vp, P(abi.PowerParams)]),
         "swh_gspace_power_spectrum_result": (C.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "swh_gspace_power_spectrum_times": (C.c_int, [vp, P(C.c_float)]),
+        "swh_gspace_lightcone_crossings": (C.c_int, [vp, P(abi.LightconeParams)]),
+        "swh_gspace_lightcone_result": (C.c_int, [vp, P(abi.LightconeResult)]),
+        "swh_gspace_lightcone_records": (C.c_int, [vp, vp, i64]),
+        "swh_gspace_lightcone_times": (C.c_int, [vp, P(C.c_float)]),
     }
     missing = [name for name in sigs if not hasattr(lib, name)]
     if missing:
@@ -1186,6 +1192,54 @@ class GravSpace:
         _check(self._lib.swh_gspace_power_spectrum_times(self.handle, ms),
                "gspace_power_spectrum_times", self._lib)
         return dict(zip(abi.POWER_STAGES, map(float, ms)))
+
+    # ---- lightcone particle crossings (swh_lightcone.hip) ------------------
+    def lightcone_enqueue(self, P: abi.LightconeParams):
+        """Queue one lightcone's crossing pass on the gspace's stream."""
+        _check(self._lib.swh_gspace_lightcone_crossings(self.handle, C.byref(P)),
+               "gspace_lightcone_crossings", self._lib)
+
+    def lightcone_result(self) -> dict:
+        """Wait for the last lightcone_enqueue; its counts."""
+        r = abi.LightconeResult()
+        _check(self._lib.swh_gspace_lightcone_result(self.handle, C.byref(r)),
+               "gspace_lightcone_result", self._lib)
+        return r.as_dict()
+
+    def lightcone_records(self, n: int) -> np.ndarray:
+        """The first n stored records, sorted by (gpart, replication)."""
+        out = np.zeros(int(n), dtype=abi.LIGHTCONE_RECORD_DTYPE)
+        _check(self._lib.swh_gspace_lightcone_records(self.handle, _ptr(out), int(n)),
+               "gspace_lightcone_records", self._lib)
+        return out
+
+    def lightcone_crossings(self, P: abi.LightconeParams) -> tuple:
+        """The crossings of the gparts as they are, for the drift P describes:
+        (records, counts). P.capacity is the first buffer size; when the pass
+        finds more than it stored, the buffer grows to what the pass asked for
+        and the pass runs again (it changes nothing, so this is legal until
+        the drift is queued). P.capacity is left at the size that sufficed."""
+        self.lightcone_enqueue(P)
+        res = self.lightcone_result()
+        res["passes"] = 1
+        while res["n_crossings"] > res["n_stored"]:
+            if res["n_slots"] <= P.capacity:
+                raise RuntimeError(f"gspace_lightcone_crossings: {res['n_stored']} of "
+                                   f"{res['n_crossings']} crossings stored with "
+                                   f"{res['n_slots']} of {P.capacity} slots in use")
+            P.capacity = int(res["n_slots"])
+            passes = res["passes"]
+            self.lightcone_enqueue(P)
+            res = self.lightcone_result()
+            res["passes"] = passes + 1
+        return self.lightcone_records(res["n_stored"]), res
+
+    def lightcone_ms(self) -> dict:
+        """HIP-event times (ms) of the stages of the last lightcone pass."""
+        ms = (C.c_float * 2)()
+        _check(self._lib.swh_gspace_lightcone_times(self.handle, ms), "gspace_lightcone_times",
+               self._lib)
+        return dict(zip(abi.LIGHTCONE_STAGES, map(float, ms)))
 
     def sync(self):
         _check(self._lib.swh_gspace_sync(self.handle), "gspace_sync", self._lib)
