@@ -339,7 +339,9 @@ SWH_API swh_status swh_space_unpack_halo(swh_space *s, const int32_t *idx, int32
  * src/hydro/SPHENIX/hydro.h:1012-1066; entropy and pressure floors NONE):
  * x += v_full dt_drift; v += a_hydro dt_kick_hydro (+ a_grav dt_kick_grav for
  * particles with a gpart); u += u_dt dt_therm; h, rho by exp(+-w1); u floored
- * at min_u; P, c from the EOS; v_sig >= 2c. Every non-inhibited particle,
+ * at min_u; P, c from the EOS; v_sig >= 2c; then h limited to [P->h_min,
+ * P->h_max] of the swh_hydro_params (cell_drift.c:314-316), which is the h
+ * the space's largest-h tracking sees. Every non-inhibited particle,
  * owned or foreign, is drifted. The particles stay in their cells: the loops
  * widen their reach by the largest displacement since the last rebuild
  * (swh_space_info.dx_max, SWIFT's dx_max_part), so they stay exact; rebuild

@@ -1231,11 +1231,13 @@ API void PFX(box_extra_ghost)(struct part *parts, long long N,
 /* Drift of every non-inhibited particle: drift_part (src/drift.h:143-232)
  * with SPHENIX hydro_predict_extra (src/hydro/SPHENIX/hydro.h:1012-1066),
  * entropy and pressure floors NONE, EOS_IDEAL_GAS. Float fields in float, as
- * the reference (both builds: the drift has no reduction). has_gpart[i]:
- * the part has a gpart (gravity kick). */
+ * the reference (both builds: the drift has no reduction), then h limited to
+ * [h_min, h_max] as cell_drift.c:314-316 does after the prediction.
+ * has_gpart[i]: the part has a gpart (gravity kick). */
 struct oracle_drift_params {
   double dt_drift, dt_kick_hydro, dt_kick_grav, dt_therm;
   float min_u;
+  float h_max, h_min; /* hydro_props: h is limited to them (cell_drift.c:314-316) */
 };
 
 static float approx_expf_o(float x) {  /* src/approx_math.h:35 */
@@ -1287,6 +1289,9 @@ API void PFX(box_drift)(struct part *parts, struct xpart *xparts, const char *ha
       xp->x_diff[k] -= dx;
       xp->x_diff_sort[k] -= dx;
     }
+    /* cell_drift.c:314-316: limit h to within the allowed range */
+    p->h = p->h < D->h_max ? p->h : D->h_max;
+    p->h = p->h > D->h_min ? p->h : D->h_min;
   }
 }
 

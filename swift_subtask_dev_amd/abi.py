@@ -251,10 +251,19 @@ class LimiterResult(C.Structure):
 
 
 class DriftParams(C.Structure):
-    """swh_drift_params (== the oracle's oracle_drift_params)."""
+    """swh_drift_params, and behind it the two floats the oracle's
+    oracle_drift_params adds: the [h_min, h_max] its box_drift limits h to
+    (cell_drift.c:314-316). swh_space_drift reads only the swh_drift_params
+    prefix and takes the limits from its swh_hydro_params. The defaults are
+    default_hydro_params' (inert)."""
 
     _fields_ = [("dt_drift", C.c_double), ("dt_kick_hydro", C.c_double),
-                ("dt_kick_grav", C.c_double), ("dt_therm", C.c_double), ("min_u", C.c_float)]
+                ("dt_kick_grav", C.c_double), ("dt_therm", C.c_double), ("min_u", C.c_float),
+                ("h_max", C.c_float), ("h_min", C.c_float)]
+
+    def __init__(self, dt_drift=0.0, dt_kick_hydro=0.0, dt_kick_grav=0.0, dt_therm=0.0,
+                 min_u=0.0, h_max=float(np.finfo(np.float32).max), h_min=0.0):
+        super().__init__(dt_drift, dt_kick_hydro, dt_kick_grav, dt_therm, min_u, h_max, h_min)
 
 
 class GPartLayout(C.Structure):

@@ -457,10 +457,12 @@ __device__ __forceinline__ float approx_expf(float x) {
 struct DriftParams {
   double dt_drift, dt_kick_hydro, dt_kick_grav, dt_therm;
   float min_u;
+  float h_max, h_min;  // swh_hydro_params: the drift keeps h inside them
 };
 
 // drift_part (src/drift.h:143-232) + SPHENIX hydro_predict_extra
-// (hydro.h:1012-1066) per particle; float fields in the reference's float
+// (hydro.h:1012-1066) per particle, then h limited to [h_min, h_max]
+// (cell_drift.c:314-316); float fields in the reference's float
 // arithmetic, positions in double. dx_bits / h_bits: running maxima of the
 // displacement since the rebuild and of h (float bits, positive).
 // max |v_full| over the xparts (float bits; |v| >= 0 orders as its bits)
@@ -544,6 +546,9 @@ __global__ __launch_bounds__(256) void drift_kernel(SoA a, const float4* __restr
     float4 gr = a.grad[s];
     gr.x = fmaxf(gr.x, 2.f * soundspeed);
     a.grad[s] = gr;
+    // cell_drift.c:314-316: limit h to within the allowed range
+    h = fminf(h, D.h_max);
+    h = fmaxf(h, D.h_min);
     p.h = h;
     a.pos[s] = p;
     // offsets since the last rebuild (xp->x_diff)
@@ -881,7 +886,8 @@ swh_status swh_space_drift(swh_space* s, const swh_drift_params* D, const swh_hy
   }
   SWH_HIP(hipSetDevice(s->ctx->device));
   hipStream_t st = s->stream;
-  DriftParams dp{D->dt_drift, D->dt_kick_hydro, D->dt_kick_grav, D->dt_therm, D->min_u};
+  DriftParams dp{D->dt_drift, D->dt_kick_hydro, D->dt_kick_grav, D->dt_therm, D->min_u,
+                 P->h_max, P->h_min};
   unsigned int* ctr = s->counters.as<unsigned int>();
   unsigned int* dx_bits = ctr + 19;  // counter slot 19: drift displacement
   SWH_HIP(hipMemsetAsync(dx_bits, 0, sizeof(unsigned int), st));
