@@ -105,7 +105,7 @@ swh::TaskWorker* swh_context::lease() {
     if (w->busy.try_lock()) return w;
   auto* w = new swh::TaskWorker();
   if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess) {
+      hipStreamCreateWithFlags(w->stream.put(), hipStreamNonBlocking) != hipSuccess) {
     delete w;
     return nullptr;
   }
@@ -223,14 +223,6 @@ swh_status swh_finalize(swh_context* c) {
   (void)hipSetDevice(c->device);
   for (auto* w : c->workers) {
     if (w->stream) (void)hipStreamSynchronize(w->stream);
-    w->dparts.release();
-    w->dparts2.release();
-    w->dind.release();
-    w->dself.release();
-    w->dcount.release();
-    w->hstage.release();
-    w->hstage2.release();
-    if (w->stream) (void)hipStreamDestroy(w->stream);
     delete w;
   }
   delete c;

@@ -157,23 +157,6 @@ void couple_unlink(swh_gspace* g) {
   if (g && g->link) couple_unlink(g->link);
 }
 
-void couple_release(swh_space* s) {
-  couple_unlink(s);
-  s->gp_agrav_s.release();
-  s->gp_amesh_s.release();
-  s->link_mark.release();
-  s->link_cnt.release();
-  if (s->link_event) (void)hipEventDestroy(s->link_event);
-  s->link_event = nullptr;
-  s->link_timer.release();
-}
-
-void couple_release(swh_gspace* g) {
-  couple_unlink(g);
-  if (g->link_event) (void)hipEventDestroy(g->link_event);
-  g->link_event = nullptr;
-}
-
 swh_status need_link(const swh_space* s, const char* what) {
   if (s->link) return SWH_OK;
   set_error("swh_space_link_gspace must precede %s", what);
@@ -187,10 +170,10 @@ swh_status need_pull(const swh_space* s, const char* what) {
 }
 
 // `second` waits (on the device) for what is queued on `first` now.
-static swh_status order_streams(hipEvent_t* ev, hipStream_t first, hipStream_t second) {
-  if (!*ev) SWH_HIP(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-  SWH_HIP(hipEventRecord(*ev, first));
-  SWH_HIP(hipStreamWaitEvent(second, *ev, 0));
+static swh_status order_streams(Event& ev, hipStream_t first, hipStream_t second) {
+  SWH_TRY(ev.ensure(hipEventDisableTiming));
+  SWH_HIP(hipEventRecord(ev, first));
+  SWH_HIP(hipStreamWaitEvent(second, ev, 0));
   return SWH_OK;
 }
 
@@ -302,7 +285,7 @@ swh_status swh_space_pull_gravity(swh_space* s) {
   GRecLayout L;
   SWH_TRY(link_record(g, &L));
   SWH_HIP(hipSetDevice(s->ctx->device));
-  SWH_TRY(order_streams(&g->link_event, g->stream, s->stream));
+  SWH_TRY(order_streams(g->link_event, g->stream, s->stream));
   SWH_TRY(s->link_timer.begin(LT_PULL, s->stream));
   hipLaunchKernelGGL(pull_kernel, dim3(couple_grid(g->n)), dim3(256), 0, s->stream, L,
                      g->aos.as<const char>(), g->n, s->n, s->iperm.as<const int>(),
@@ -311,7 +294,7 @@ swh_status swh_space_pull_gravity(swh_space* s) {
   SWH_TRY(s->link_timer.end(LT_PULL, s->stream));
   s->gp_pulled = true;
   // the gspace's later work (a tree build moves the records) waits for the read
-  return order_streams(&s->link_event, s->stream, g->stream);
+  return order_streams(s->link_event, s->stream, g->stream);
 }
 
 swh_status swh_space_push_gparts(swh_space* s, const swh_push_params* Q) {
@@ -333,7 +316,7 @@ swh_status swh_space_push_gparts(swh_space* s, const swh_push_params* Q) {
   SWH_TRY(link_record(g, &L));
   SWH_HIP(hipSetDevice(s->ctx->device));
   if (Q->what & SWH_PUSH_V_FULL) SWH_TRY(space_ensure_xsorted(s));
-  SWH_TRY(order_streams(&s->link_event, s->stream, g->stream));
+  SWH_TRY(order_streams(s->link_event, s->stream, g->stream));
   SWH_TRY(s->link_timer.begin(LT_PUSH, g->stream));
   hipLaunchKernelGGL(push_kernel, dim3(couple_grid(g->n)), dim3(256), 0, g->stream, L,
                      g->aos.as<char>(), g->n, s->n, s->iperm.as<const int>(),
@@ -347,7 +330,7 @@ swh_status swh_space_push_gparts(swh_space* s, const swh_push_params* Q) {
     g->tree_stale = true;
   }
   // the space's later work (kicks, a rebuild) waits for the read
-  return order_streams(&g->link_event, g->stream, s->stream);
+  return order_streams(g->link_event, g->stream, s->stream);
 }
 
 swh_status swh_space_link_times(swh_space* s, float* ms) {

@@ -63,39 +63,21 @@ struct FofState {
   DevBuf box;                  // double[6] per cell: lo, hi of its linkable gparts
   DevBuf tops;                 // i32: the top-level cells
   DevBuf fr0, fr1, lpairs;     // int2: the two frontiers, the leaf pairs
-  DevBuf ctr;                  // u64[FC_SLOTS]
   DevBuf skey, skey2, sidx, sidx2;  // u32 root / i32 index, and sorted by root
   DevBuf gcnt, gstart;         // i32[n], at a root: its group's size, its first sorted slot
   DevBuf rkey, rkey2;          // u64[n]: the ranking keys and their sorted copy
   DevBuf ids;                  // i64[n]
   DevBuf gsize, gmass, gcom, groot;  // per kept group, in rank order
   DevBuf tmp;                  // hipcub scratch
-  HostBuf host;                // pinned: the counters read back
-  hipEvent_t event = nullptr;
-  bool has = false, pending = false;
+  // u64[FC_SLOTS], the counters. The walk and the catalogue read them in the
+  // middle of a call (fof_read_counters); the event stands behind the call's
+  // last kernels, which the output entries wait for.
+  Readback ctr;
   int64_t n = 0;               // the gparts of the last call
   int64_t n_leaf_pairs = 0;
   int64_t ngroups = 0;
   StageTimer<4> timer;
-  void release() {
-    DevBuf* bufs[] = {&xm, &parent, &roots, &box, &tops, &fr0, &fr1, &lpairs, &ctr, &skey, &skey2,
-                      &sidx, &sidx2, &gcnt, &gstart, &rkey, &rkey2, &ids, &gsize, &gmass, &gcom,
-                      &groot, &tmp};
-    for (DevBuf* b : bufs) b->release();
-    host.release();
-    if (event) (void)hipEventDestroy(event);
-    event = nullptr;
-    timer.release();
-    has = pending = false;
-  }
 };
-
-void fof_release(swh_gspace* g) {
-  if (!g->fof) return;
-  g->fof->release();
-  delete g->fof;
-  g->fof = nullptr;
-}
 
 struct FofDev {
   double l_x2;
@@ -492,8 +474,8 @@ __global__ __launch_bounds__(256) void fof_group_wave_kernel(
 
 // the first `count` counters to the pinned copy, and wait
 static swh_status fof_read_counters(FofState& F, int count, hipStream_t st) {
-  SWH_HIP(hipMemcpyAsync(F.host.ptr, F.ctr.ptr, (size_t)count * sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost, st));
+  SWH_HIP(hipMemcpyAsync(F.ctr.pinned.ptr, F.ctr.rec.ptr,
+                         (size_t)count * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   SWH_HIP(hipStreamSynchronize(st));
   return SWH_OK;
 }
@@ -526,8 +508,8 @@ static swh_status fof_walk(swh_gspace* g, FofState& F, const FofDev& P, hipStrea
   const int ntops = (int)g->tree_tops.size();
   const swh_gcell* cells = g->tree_d.as<const swh_gcell>();
   const double* box = F.box.as<const double>();
-  unsigned long long* ctr = F.ctr.as<unsigned long long>();
-  const unsigned long long* h = reinterpret_cast<const unsigned long long*>(F.host.ptr);
+  unsigned long long* ctr = F.ctr.dev<unsigned long long>();
+  const unsigned long long* h = F.ctr.host<unsigned long long>();
   SWH_TRY(F.tops.reserve((size_t)ntops * sizeof(int32_t)));
   SWH_HIP(hipMemcpyAsync(F.tops.ptr, g->tree_tops.data(), (size_t)ntops * sizeof(int32_t),
                          hipMemcpyHostToDevice, st));
@@ -586,7 +568,7 @@ static swh_status fof_sort_keys(FofState& F, const unsigned long long* kin,
 }
 
 static swh_status fof_ready(swh_gspace* g, const char* what, FofState** out) {
-  if (!g->fof || !g->fof->has) {
+  if (!g->fof || !g->fof->ctr.has) {
     set_error("swh_gspace_fof must precede %s", what);
     return SWH_ERR_STATE;
   }
@@ -595,11 +577,8 @@ static swh_status fof_ready(swh_gspace* g, const char* what, FofState** out) {
     return SWH_ERR_STATE;
   }
   SWH_HIP(hipSetDevice(g->ctx->device));
-  if (g->fof->pending) {
-    SWH_HIP(hipEventSynchronize(g->fof->event));
-    g->fof->pending = false;
-  }
-  *out = g->fof;
+  SWH_TRY(g->fof->ctr.wait());
+  *out = g->fof.get();
   return SWH_OK;
 }
 
@@ -618,21 +597,14 @@ swh_status swh_gspace_fof(swh_gspace* g, const swh_fof_params* Fp) {
     return SWH_ERR_STATE;
   }
   SWH_HIP(hipSetDevice(g->ctx->device));
-  if (!g->fof) g->fof = new FofState();
+  if (!g->fof) g->fof = make_owned<FofState>();
   FofState& F = *g->fof;
   hipStream_t st = g->stream;
-  SWH_TRY(F.host.reserve(FC_SLOTS * sizeof(unsigned long long)));
-  if (!F.event) SWH_HIP(hipEventCreateWithFlags(&F.event, hipEventDisableTiming));
-  if (F.pending) {
-    SWH_HIP(hipEventSynchronize(F.event));
-    F.pending = false;
-  }
+  SWH_TRY(F.ctr.wait());  // the pinned counters are the last call's until it is through
   if (g->n == 0) {  // an empty set: zero counts, nothing queued
-    std::memset(F.host.ptr, 0, FC_SLOTS * sizeof(unsigned long long));
     F.n = 0;
     F.n_leaf_pairs = F.ngroups = 0;
-    F.has = true;
-    return SWH_OK;
+    return F.ctr.set_host(nullptr, FC_SLOTS * sizeof(unsigned long long));
   }
   const int ncells = (int)g->tree.size();
   if (ncells == 0) {
@@ -651,14 +623,14 @@ swh_status swh_gspace_fof(swh_gspace* g, const swh_fof_params* Fp) {
   }
   const GRecLayout L = grec_layout(g);
   SWH_TRY(grec_require(L, kNeedFof | (g->step_layout_set ? GF_TYPE : 0u), "swh_gspace_fof"));
-  F.has = false;
+  F.ctr.invalidate();
   const int n = (int)g->n;
   const size_t N = (size_t)n;
   SWH_TRY(F.xm.reserve(N * sizeof(double4)));
   SWH_TRY(F.parent.reserve(N * 4));
   SWH_TRY(F.roots.reserve(N * 4));
   SWH_TRY(F.box.reserve((size_t)ncells * 6 * sizeof(double)));
-  SWH_TRY(F.ctr.reserve(FC_SLOTS * sizeof(unsigned long long)));
+  SWH_TRY(F.ctr.prepare(FC_SLOTS * sizeof(unsigned long long)));
   SWH_TRY(F.skey.reserve(N * 4));
   SWH_TRY(F.skey2.reserve(N * 4));
   SWH_TRY(F.sidx.reserve(N * 4));
@@ -668,7 +640,7 @@ swh_status swh_gspace_fof(swh_gspace* g, const swh_fof_params* Fp) {
   SWH_TRY(F.rkey.reserve(N * 8));
   SWH_TRY(F.rkey2.reserve(N * 8));
   SWH_TRY(F.ids.reserve(N * 8));
-  unsigned long long* ctr = F.ctr.as<unsigned long long>();
+  unsigned long long* ctr = F.ctr.dev<unsigned long long>();
   const dim3 ngrid((unsigned)((n + 255) / 256));
 
   // ---- leaf pairs ----
@@ -718,7 +690,7 @@ swh_status swh_gspace_fof(swh_gspace* g, const swh_fof_params* Fp) {
                         n, st));
   // the number of kept groups sizes the per-group outputs and launches
   SWH_TRY(fof_read_counters(F, FC_SLOTS, st));
-  const int ngroups = (int)reinterpret_cast<const unsigned long long*>(F.host.ptr)[FC_GROUPS];
+  const int ngroups = (int)F.ctr.host<unsigned long long>()[FC_GROUPS];
   const size_t NG = (size_t)std::max(1, ngroups);
   SWH_TRY(F.gsize.reserve(NG * 8));
   SWH_TRY(F.gmass.reserve(NG * 8));
@@ -739,18 +711,16 @@ swh_status swh_gspace_fof(swh_gspace* g, const swh_fof_params* Fp) {
     SWH_HIP(hipGetLastError());
   }
   SWH_TRY(F.timer.end(FT_CATALOGUE, st));
-  SWH_HIP(hipEventRecord(F.event, st));
   F.n = g->n;
   F.ngroups = ngroups;
-  F.pending = F.has = true;
-  return SWH_OK;
+  return F.ctr.mark(st);
 }
 
 swh_status swh_gspace_fof_result(swh_gspace* g, swh_fof_result* out) {
   if (!g || !out) return SWH_ERR_ARG;
   FofState* F = nullptr;
   SWH_TRY(fof_ready(g, "swh_gspace_fof_result", &F));
-  const unsigned long long* h = reinterpret_cast<const unsigned long long*>(F->host.ptr);
+  const unsigned long long* h = F->ctr.host<unsigned long long>();
   out->n_linkable = (int64_t)h[FC_LINKABLE];
   out->n_groups = (int64_t)h[FC_GROUPS];
   out->n_in_groups = (int64_t)h[FC_IN_GROUPS];

@@ -166,11 +166,6 @@ __global__ __launch_bounds__(256) void gstep_kernel(GRecLayout L, char* __restri
   part.commit<kRecStrideGspace, TS, false>(rec, n_updated, n_below);
 }
 
-void gstep_release(swh_gspace* g) {
-  g->gstep.release();
-  g->gstep_timer.release();
-}
-
 // The stages of swh_gspace.gstep_timer (swh_gspace_step_times).
 enum { GT_DRIFT = 0, GT_INIT, GT_END_FORCE, GT_STEP };
 

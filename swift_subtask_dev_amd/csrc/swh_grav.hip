@@ -1285,7 +1285,7 @@ swh_status swh_gspace_create(swh_context* ctx, swh_gspace** out) {
   const bool high = !(pe && pe[0] == '0');
   hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
   if (e == hipSuccess)
-    e = hipStreamCreateWithPriority(&g->stream, hipStreamNonBlocking, high ? greatest : least);
+    e = hipStreamCreateWithPriority(g->stream.put(), hipStreamNonBlocking, high ? greatest : least);
   if (e != hipSuccess) {
     delete g;
     return SWH_ERR_HIP;
@@ -1298,24 +1298,8 @@ swh_status swh_gspace_destroy(swh_gspace* g) {
   if (!g) return SWH_OK;
   (void)hipSetDevice(g->ctx->device);
   (void)hipStreamSynchronize(g->stream);
-  DevBuf* bufs[] = {&g->aos,      &g->pos,      &g->hinv,    &g->mass,    &g->active,
-                    &g->accel,    &g->oagn,     &g->mpoles,  &g->leaves,  &g->pair_off,
-                    &g->pairs,    &g->counter,  &g->cell_act, &g->ftens,  &g->m2l_off,
-                    &g->m2l_src,  &g->l2l_list, &g->leaf_ids, &g->leaf_of, &g->m2m_list, &g->tree_d, &g->wf0,
-                    &g->wf1,      &g->pp_key,  &g->pp_val,  &g->pp_key2,
-                    &g->pp_val2,  &g->mm_key,  &g->mm_val,  &g->mm_key2,
-                    &g->mm_val2,  &g->wsort_tmp, &g->wrec, &g->wcnt, &g->wbase, &g->owned_d,
-                    &g->m2p_bits};
-  for (DevBuf* b : bufs) b->release();
-  mesh_release(g);
-  gtree_release(g);
-  gstep_release(g);
-  couple_release(g);
-  fof_release(g);
-  power_release(g);
-  lightcone_release(g);
-  (void)hipStreamDestroy(g->stream);
-  delete g;
+  couple_unlink(g);
+  delete g;  // every member frees what it owns, the stream last
   return SWH_OK;
 }
 

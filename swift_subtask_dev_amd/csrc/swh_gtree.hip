@@ -310,20 +310,6 @@ static int gt_bits(uint64_t v) {  // bits needed for values 0 .. v
   return b;
 }
 
-void gtree_release(swh_gspace* g) {
-  DevBuf* bufs[] = {&g->gt_mort,  &g->gt_mort2,  &g->gt_tkey, &g->gt_tkey2, &g->gt_idx,
-                    &g->gt_idx2,  &g->gt_aos2,   &g->gt_order, &g->gt_order2, &g->gt_tmp,
-                    &g->gt_tstart, &g->gt_cnt,   &g->gt_scan, &g->gt_bcell, &g->gt_pk,
-                    &g->gt_pk2,   &g->gt_pv,     &g->gt_pv2,  &g->gt_rank,  &g->gt_flag};
-  for (DevBuf* b : bufs) b->release();
-  g->gt_host.release();
-  for (auto& e : g->gt_ev)
-    if (e) {
-      (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-}
-
 swh_status gtree_fill_leaf_of(swh_gspace* g, int32_t ncells) {
   if (ncells <= 0) return SWH_OK;
   const int per = kGtBlock / 64;
@@ -367,8 +353,7 @@ swh_status swh_gspace_build_tree(swh_gspace* g, const swh_tree_params* T, int32_
   const int cdim = T->cdim, ntop = cdim * cdim * cdim;
   const double box = T->box, w = box / (double)cdim;
   hipStream_t st = g->stream;
-  for (auto& e : g->gt_ev)
-    if (!e) SWH_HIP(hipEventCreate(&e));
+  for (Event& e : g->gt_ev) SWH_TRY(e.ensure());
 
   const size_t N = (size_t)n;
   SWH_TRY(g->gt_mort.reserve(N * 8));

@@ -673,17 +673,9 @@ swh_status swh_grav_tree_tasks(swh_gspace* g, const swh_grav_params* G,
   SWH_HIP(hipSetDevice(g->ctx->device));
   SWH_TRY(launch_unpack(g, G->max_active_bin));  // activity, accumulators
   // multipoles: P2M at the leaves, M2M up the tree (space_split.c:340-440)
-  // the phase events, destroyed on every exit path (SWH_TRY / SWH_HIP return early)
-  struct Events {
-    hipEvent_t e[6] = {};
-    ~Events() {
-      for (auto& x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-  } evs;
-  hipEvent_t* ev = evs.e;
+  Event ev[6];  // the phase events, this call's
   if (stats) {
-    for (int k = 0; k < 6; k++) SWH_HIP(hipEventCreate(&ev[k]));
+    for (Event& e : ev) SWH_TRY(e.ensure());
     SWH_HIP(hipEventRecord(ev[0], g->stream));
   }
   SWH_TRY(tree_multipoles(g));

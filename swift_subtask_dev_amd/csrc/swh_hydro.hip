@@ -1272,19 +1272,12 @@ swh_status swh_ghost(swh_space* s, const swh_hydro_params* P, int32_t* iteration
   // past their list reach, and the ghost / host + rebuild / rerun times (the
   // passes then run synchronously)
   static const bool dbg = std::getenv("SWH_GHOST_DEBUG") != nullptr;
-  hipEvent_t dev[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event dev[4];
   if (dbg)
-    for (auto& e : dev) SWH_HIP(hipEventCreate(&e));
+    for (Event& e : dev) SWH_TRY(e.ensure());
   // the copies of the passes' counts (the host waits on these, not the stream)
-  struct CountEvents {
-    hipEvent_t e[2] = {nullptr, nullptr};
-    ~CountEvents() {
-      for (auto& x : e)
-        if (x) (void)hipEventDestroy(x);
-    }
-    hipEvent_t& operator[](int k) { return e[k]; }
-  } ev_cnt;
-  for (int k = 0; k < 2; k++) SWH_HIP(hipEventCreateWithFlags(&ev_cnt.e[k], hipEventDisableTiming));
+  Event ev_cnt[2];
+  for (Event& e : ev_cnt) SWH_TRY(e.ensure(hipEventDisableTiming));
   auto launch_pass = [&](int k, const SegList& in, int grid_items) -> swh_status {
     const float* lreach = (lists && s->list_valid) ? s->nbr_reach.as<const float>() : nullptr;
     const int g = (grid_items + block - 1) / block;
@@ -1372,8 +1365,6 @@ swh_status swh_ghost(swh_space* s, const swh_hydro_params* P, int32_t* iteration
     it = k + 1;
     debug_line(k, in_count, count, false);
   }
-  if (dbg)
-    for (auto& e : dev) (void)hipEventDestroy(e);
   {
     // slots 2 (max h) .. 17 (list-stale flag) in one read
     unsigned int c[18];

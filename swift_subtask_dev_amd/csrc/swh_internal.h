@@ -6,77 +6,15 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "swifthip.h"
+#include "swh_device.h"
 
 namespace swh {
-
-// ---------------------------------------------------------------------------
-// Errors: thread-local message + status codes, no aborts.
-// ---------------------------------------------------------------------------
-void set_error(const char* fmt, ...);
-
-#define SWH_HIP(call)                                                           \
-  do {                                                                          \
-    hipError_t _e = (call);                                                     \
-    if (_e != hipSuccess) {                                                     \
-      ::swh::set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(_e),   \
-                       __FILE__, __LINE__);                                     \
-      return (_e == hipErrorOutOfMemory) ? SWH_ERR_OOM : SWH_ERR_HIP;           \
-    }                                                                           \
-  } while (0)
-
-#define SWH_TRY(expr)                      \
-  do {                                     \
-    swh_status _s = (expr);                \
-    if (_s != SWH_OK) return _s;           \
-  } while (0)
-
-// Growable device buffer (never shrinks; reused across calls so the loops do
-// no allocation once warm).
-struct DevBuf {
-  void* ptr = nullptr;
-  size_t bytes = 0;
-  swh_status reserve(size_t b) {
-    if (b <= bytes) return SWH_OK;
-    if (ptr) {
-      hipError_t e = hipFree(ptr);
-      (void)e;
-      ptr = nullptr;
-      bytes = 0;
-    }
-    size_t nb = b < 256 ? 256 : b;
-    hipError_t e = hipMalloc(&ptr, nb);
-    if (e != hipSuccess) {
-      set_error("hipMalloc(%zu) failed: %s", nb, hipGetErrorString(e));
-      return SWH_ERR_OOM;
-    }
-    bytes = nb;
-    return SWH_OK;
-  }
-  void release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    bytes = 0;
-  }
-  // Grow (at least doubling) keeping the first `used` bytes; the stream is
-  // waited for before the old buffer goes, whatever work still reads it.
-  swh_status grow_keep(size_t need, size_t used, hipStream_t stream) {
-    if (need <= bytes) return SWH_OK;
-    DevBuf nb;
-    SWH_TRY(nb.reserve(need > 2 * bytes ? need : 2 * bytes));
-    if (used > 0) SWH_HIP(hipMemcpyAsync(nb.ptr, ptr, used, hipMemcpyDeviceToDevice, stream));
-    SWH_HIP(hipStreamSynchronize(stream));
-    release();
-    *this = nb;
-    return SWH_OK;
-  }
-  template <typename T>
-  T* as() const { return reinterpret_cast<T*>(ptr); }
-};
 
 // hipcub's two-call idiom: call(nullptr, bytes) asks for the scratch size,
 // `tmp` is grown to it, call(tmp.ptr, bytes) runs.
@@ -90,51 +28,23 @@ swh_status cub_run(DevBuf& tmp, Call&& call) {
   return SWH_OK;
 }
 
-// Pinned host staging buffer.
-struct HostBuf {
-  void* ptr = nullptr;
-  size_t bytes = 0;
-  swh_status reserve(size_t b) {
-    if (b <= bytes) return SWH_OK;
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = nullptr;
-    size_t nb = b < 4096 ? 4096 : b;
-    hipError_t e = hipHostMalloc(&ptr, nb, hipHostMallocDefault);
-    if (e != hipSuccess) {
-      set_error("hipHostMalloc(%zu) failed: %s", nb, hipGetErrorString(e));
-      bytes = 0;
-      return SWH_ERR_OOM;
-    }
-    bytes = nb;
-    return SWH_OK;
-  }
-  void release() {
-    if (ptr) (void)hipHostFree(ptr);
-    ptr = nullptr;
-    bytes = 0;
-  }
-};
-
 // The step record of a space or a gspace, host side: the u64 slots a time step
-// reduces into on the device, their pinned copy and the event behind the last
-// copy. swh_steprec.h has the slots, the kernels' side and these methods.
+// reduces into on the device and their readback. swh_steprec.h has the slots,
+// the kernels' side and these methods.
 constexpr int kRecStrideSpace = 1;    // u64 from one slot to the next: packed,
 constexpr int kRecStrideGspace = 16;  // one slot per 128 bytes
 struct StepRecord {
   int stride;
-  DevBuf rec;
-  HostBuf host;
-  hipEvent_t event = nullptr;  // behind the last record copy
-  bool pending = false;        // a record copy is queued and not yet read
-  bool has_ts = false;         // the record holds a timestep's fields
-  double dt_min = 0.;          // of that timestep (decode's message)
-  float vmax = 0.f;            // max |v_full| of the last fetched record
+  Readback rb;          // pending: a record copy is queued and not yet read
+  bool has_ts = false;  // the record holds a timestep's fields
+  double dt_min = 0.;   // of that timestep (decode's message)
+  float vmax = 0.f;     // max |v_full| of the last fetched record
   explicit StepRecord(int stride_) : stride(stride_) {}
-  unsigned long long* dev() const { return rec.as<unsigned long long>(); }
+  unsigned long long* dev() const { return rb.dev<unsigned long long>(); }
   // before a launch: the buffers and the event; the timestep's fields stay
   // until the next timestep (ts), every launch measures max |v_full| anew
   swh_status prepare(hipStream_t st, bool ts);
-  swh_status readback(hipStream_t st);  // after it: queue the copy to the host
+  swh_status readback(hipStream_t st) { return rb.queue(st); }  // after it
   void note_timestep(double dt_min_) {
     has_ts = true;
     dt_min = dt_min_;
@@ -142,88 +52,27 @@ struct StepRecord {
   swh_status fetch();  // wait for a queued copy; vmax
   // the fetched record; noun: what the record counts ("parts", "gparts")
   swh_status decode(swh_step_result* out, const char* noun) const;
-  void invalidate() { pending = has_ts = false; }
-  void release();
-};
-
-// HIP events around the last launch of each of N stages.
-template <int N>
-struct StageTimer {
-  hipEvent_t ev[N][2] = {};
-  bool timed[N] = {};
-  swh_status begin(int k, hipStream_t st) {
-    for (auto& e : ev[k])
-      if (!e) SWH_HIP(hipEventCreate(&e));
-    SWH_HIP(hipEventRecord(ev[k][0], st));
-    return SWH_OK;
-  }
-  swh_status end(int k, hipStream_t st) {
-    SWH_HIP(hipEventRecord(ev[k][1], st));
-    timed[k] = true;
-    return SWH_OK;
-  }
-  // ms[k]: the last launch of stage k, -1 if it never ran; waits for it
-  swh_status read(float* ms) {
-    for (int k = 0; k < N; k++) {
-      ms[k] = -1.f;
-      if (!timed[k]) continue;
-      SWH_HIP(hipEventSynchronize(ev[k][1]));
-      SWH_HIP(hipEventElapsedTime(&ms[k], ev[k][0], ev[k][1]));
-    }
-    return SWH_OK;
-  }
-  void release() {
-    for (auto& pair : ev)
-      for (auto& e : pair)
-        if (e) {
-          (void)hipEventDestroy(e);
-          e = nullptr;
-        }
+  void invalidate() {
+    rb.invalidate();
+    has_ts = false;
   }
 };
 
 // The statistics of a space or a gspace (swh_stats.hip), host side: the
-// blocks' partial sums, the reduced record, its pinned copy and the event
-// behind the last copy; the scratch of the synchronised velocities; HIP events
-// around the last statistics and the last velocity launch.
+// blocks' partial sums, the reduced record and its readback; the scratch of
+// the synchronised velocities; HIP events around the last statistics and the
+// last velocity launch.
 struct StatsState {
-  DevBuf partials, out, vel;
-  HostBuf host;
-  hipEvent_t event = nullptr;
-  bool pending = false;  // a copy is queued and not yet waited for
-  bool has = false;      // host holds the result of some call
-  StageTimer<2> timer;   // statistics (both kernels), sync velocities
-  void release() {
-    partials.release();
-    out.release();
-    vel.release();
-    host.release();
-    if (event) (void)hipEventDestroy(event);
-    event = nullptr;
-    timer.release();
-    pending = has = false;
-  }
-  ~StatsState() { release(); }  // with its space (swh_space_destroy's delete)
+  DevBuf partials, vel;
+  Readback rb;
+  StageTimer<2> timer;  // statistics (both kernels), sync velocities
 };
 
 // The displacement-constraint sums of a space or a gspace (swh_rms.hip), host
-// side: the blocks' partial records, the reduced record, its pinned copy and
-// the event behind the last copy.
+// side: the blocks' partial records, the reduced record and its readback.
 struct RmsState {
-  DevBuf partials, out;
-  HostBuf host;
-  hipEvent_t event = nullptr;
-  bool pending = false;  // a copy is queued and not yet waited for
-  bool has = false;      // host holds the result of some call
-  void release() {
-    partials.release();
-    out.release();
-    host.release();
-    if (event) (void)hipEventDestroy(event);
-    event = nullptr;
-    pending = has = false;
-  }
-  ~RmsState() { release(); }  // with its space (the destroy calls' delete)
+  DevBuf partials;
+  Readback rb;
 };
 
 // The friends-of-friends search of a gspace (swh_fof.hip): its scratch, its
@@ -237,6 +86,18 @@ struct PowerState;
 // The lightcone pass of a gspace (swh_lightcone.hip): the replication list,
 // the two record buffers, the sort's scratch, the pinned copy of the counters.
 struct LightconeState;
+
+// The hipFFT plans of the PM mesh (swh_mesh.hip).
+struct MeshPlans;
+
+// An owning pointer to a type that is complete only in the file that makes the
+// object: the deleter is set there, by make_owned.
+template <typename T>
+using Owned = std::unique_ptr<T, void (*)(T*)>;
+template <typename T>
+Owned<T> make_owned() {
+  return Owned<T>(new T(), [](T* x) { delete x; });
+}
 
 // Device copy of the AoS layout (offsets), passed by value to kernels.
 struct Layout {
@@ -259,7 +120,7 @@ swh_status make_glayout(const swh_gpart_layout* L, GLayout* out);
 
 // Per-task worker: one stream + staging buffers, leased per host thread.
 struct TaskWorker {
-  hipStream_t stream = nullptr;
+  Stream stream;  // first: destroyed after the buffers its work used
   DevBuf dparts, dparts2, dind, dself, dcount;
   HostBuf hstage, hstage2;
   std::mutex busy;
@@ -296,9 +157,12 @@ constexpr float kDefaultListSkin = SWH_DEFAULT_LIST_SKIN;
 // Device-resident particle set, sorted by grid cell in Morton order of the
 // cells (cell_rank maps a linear x-fastest cell index to its Morton rank).
 struct swh_space {
+  // The stream this space made. Declared first: members are destroyed in
+  // reverse order, so it goes after everything recorded on or allocated for
+  // it. Empty once the caller's stream is in use (swh_space_set_stream).
+  swh::Stream owned_stream;
+  hipStream_t stream = nullptr;  // the one in use: owned_stream's or the caller's
   swh_context* ctx = nullptr;
-  hipStream_t stream = nullptr;
-  bool own_stream = true;
   int64_t n = 0;
   bool built = false;
   SwhGrid grid;
@@ -345,13 +209,11 @@ struct swh_space {
   // (i32, the reference's int8 limiter_data.wakeup widened for the integer
   // atomic max of the neighbour loop), authoritative in sorted order
   // (wake_sorted) or, across a re-sort, in caller order (wake_caller);
-  // neither: every particle is not awake. lim_rec: u32[4] counts of the last
-  // apply, read back into lim_host behind lim_event.
-  swh::DevBuf wake_s, wake_c, lim_rec;
+  // neither: every particle is not awake. lim: u32[4] counts of the last apply
+  // and their readback.
+  swh::DevBuf wake_s, wake_c;
   bool wake_sorted = false, wake_caller = false;
-  swh::HostBuf lim_host;
-  hipEvent_t lim_event = nullptr;
-  bool lim_has = false;
+  swh::Readback lim;
   // a limiter loop ran since the last apply: only the loop sets wake-ups and
   // the apply resets them all, so an apply without one has nothing to do
   bool wake_dirty = false;
@@ -363,7 +225,7 @@ struct swh_space {
   swh::DevBuf gp_agrav_s, gp_amesh_s;
   bool gp_pulled = false;
   swh::DevBuf link_mark, link_cnt;  // i32[n] parts named, u32[4] the check's counts
-  hipEvent_t link_event = nullptr;  // recorded on this space's stream for the gspace's
+  swh::Event link_event;  // recorded on this space's stream for the gspace's
   // the last pull, push and linked kick / timestep launch (swh_space_link_times)
   swh::StageTimer<3> link_timer;
   swh::StatsState stats;  // swh_space_statistics / _sync_velocities (swh_stats.hip)
@@ -421,8 +283,10 @@ swh_status space_apply_pending(swh_space* s);
 }  // namespace swh
 
 struct swh_gspace {
+  // Declared first: members are destroyed in reverse order, so the stream goes
+  // after everything recorded on or allocated for it.
+  swh::Stream stream;
   swh_context* ctx = nullptr;
-  hipStream_t stream = nullptr;
   int64_t n = 0;
   swh::DevBuf aos;
   swh::GLayout layout{};
@@ -465,12 +329,11 @@ struct swh_gspace {
   swh::DevBuf tree_d, wf0, wf1, pp_key, pp_val, pp_key2, pp_val2;
   swh::DevBuf mm_key, mm_val, mm_key2, mm_val2, wsort_tmp, wrec, wcnt, wbase;
   // PM mesh (swh_gspace_pm_mesh): density / potential mesh, its r2c
-  // transform and the cached hipFFT plans of side mesh_N
+  // transform and the cached hipFFT plans of side mesh_N (swh_mesh.hip's
+  // MeshPlans, made by the first call)
   swh::DevBuf mesh_rho, mesh_frho;
   int32_t mesh_N = 0;
-  bool mesh_plans_valid = false;
-  void* mesh_fwd = nullptr;
-  void* mesh_inv = nullptr;
+  swh::Owned<swh::MeshPlans> mesh_plans{nullptr, nullptr};
   // device tree build (swh_gspace_build_tree, swh_gtree.hip). Scratch is kept
   // across builds: a rebuild of a set of the same size allocates nothing.
   bool uploaded = false;      // swh_gspace_upload was called
@@ -488,7 +351,7 @@ struct swh_gspace {
   swh::DevBuf gt_pk, gt_pk2, gt_pv, gt_pv2, gt_rank;  // preorder ranking
   swh::DevBuf gt_flag;             // i32: a non-finite position was seen
   swh::HostBuf gt_host;            // pinned: the level counts and the flag read back
-  hipEvent_t gt_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  swh::Event gt_ev[6];
   bool gt_timed = false;           // gt_ev bracket a finished build
   // device-resident step (swh_gkick.hip): the step's fields beside `layout`,
   // the record the step kernel reduces into and its pinned copy
@@ -500,32 +363,25 @@ struct swh_gspace {
   swh::StageTimer<4> gstep_timer;
   // gas <-> gpart link (swh_couple.hip)
   swh_space* link = nullptr;
-  hipEvent_t link_event = nullptr;  // recorded on this gspace's stream for the space's
+  swh::Event link_event;  // recorded on this gspace's stream for the space's
   swh::StatsState stats;  // swh_gspace_statistics / _sync_velocities (swh_stats.hip)
   swh::RmsState rms;      // swh_gspace_displacement_sums (swh_rms.hip)
-  swh::FofState* fof = nullptr;  // swh_gspace_fof (swh_fof.hip), made by the first call
-  swh::PowerState* power = nullptr;  // swh_gspace_power_spectrum (swh_power.hip), likewise
-  swh::LightconeState* lightcone = nullptr;  // swh_gspace_lightcone_crossings, likewise
+  // The analyses' states, made by the first call of each with the deleter of
+  // the file that knows the type (swh::make_owned).
+  swh::Owned<swh::FofState> fof{nullptr, nullptr};  // swh_gspace_fof (swh_fof.hip)
+  swh::Owned<swh::PowerState> power{nullptr, nullptr};  // swh_gspace_power_spectrum
+  swh::Owned<swh::LightconeState> lightcone{nullptr, nullptr};  // swh_gspace_lightcone_crossings
 };
 
 namespace swh {
-void fof_release(swh_gspace* g);   // swh_fof.hip: the search's buffers, event and timer
-void power_release(swh_gspace* g);  // swh_power.hip: the spectra's grids, plans, events
-void lightcone_release(swh_gspace* g);  // swh_lightcone.hip: the pass's buffers, event, timer
-void mesh_release(swh_gspace* g);  // swh_mesh.hip: mesh buffers and hipFFT plans
-void gtree_release(swh_gspace* g);  // swh_gtree.hip: the tree build's scratch and events
-void gstep_release(swh_gspace* g);  // swh_gkick.hip: the step record and the stage timer
 // swh_gtree.hip: the bookkeeping of a cell table, shared by swh_gspace_set_tree
 // and swh_gspace_build_tree. device_built: the table is already in tree_d and
 // leaf_of is filled on the device (gtree_fill_leaf_of), nothing O(N) on the host.
 swh_status gtree_install(swh_gspace* g, const swh_gcell* cells, int32_t ncells, bool device_built);
 swh_status gtree_fill_leaf_of(swh_gspace* g, int32_t ncells);  // swh_gtree.hip
-// swh_couple.hip: drop the link of either object (both sides forget it); the
-// _release calls also free the link's buffers and event (the destroy calls)
+// swh_couple.hip: drop the link of either object (both sides forget it)
 void couple_unlink(swh_space* s);
 void couple_unlink(swh_gspace* g);
-void couple_release(swh_space* s);
-void couple_release(swh_gspace* g);
 enum { LT_PULL = 0, LT_PUSH, LT_STEP };  // the stages of swh_space.link_timer
 // what the entries of a linked space ask: a link, and (past the empty space)
 // this step's gravity pulled

@@ -384,7 +384,7 @@ swh_status space_kick1_linked(swh_space* s, const swh_kick_params* K1, const swh
 
 // The latest record's max |v_full| bounds the next drift's displacement.
 swh_status space_fetch_step_record(swh_space* s) {
-  if (!s->step.pending) return SWH_OK;
+  if (!s->step.rb.pending) return SWH_OK;
   SWH_TRY(s->step.fetch());
   s->vfull_max = (double)s->step.vmax;
   return SWH_OK;

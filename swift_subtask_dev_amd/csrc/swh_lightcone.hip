@@ -60,33 +60,13 @@ struct LightconeState {
   DevBuf rec, rec2;       // swh_lightcone_record[capacity]: in slot order, sorted
   DevBuf key, key2;       // u64[capacity]
   DevBuf idx, idx2;       // i32[capacity]: the slot
-  DevBuf ctr;             // u64[LC_COUNT]
   DevBuf tmp;             // hipcub scratch
-  HostBuf host;           // pinned: the counters read back
+  Readback ctr;           // u64[LC_COUNT], the counters
   HostBuf host_reps;      // pinned: the list on its way to the device
-  hipEvent_t event = nullptr;
-  bool has = false, pending = false;
   int64_t n = 0;          // the gparts of the last call
   int64_t capacity = 0;   // of the last call
   StageTimer<2> timer;
-  void release() {
-    DevBuf* bufs[] = {&reps, &rec, &rec2, &key, &key2, &idx, &idx2, &ctr, &tmp};
-    for (DevBuf* b : bufs) b->release();
-    host.release();
-    host_reps.release();
-    if (event) (void)hipEventDestroy(event);
-    event = nullptr;
-    timer.release();
-    has = pending = false;
-  }
 };
-
-void lightcone_release(swh_gspace* g) {
-  if (!g->lightcone) return;
-  g->lightcone->release();
-  delete g->lightcone;
-  g->lightcone = nullptr;
-}
 
 struct LcDev {
   LightconeShell S;
@@ -389,7 +369,7 @@ static swh_status lc_params(const swh_lightcone_params* P, LcDev* d) {
 }
 
 static swh_status lc_ready(swh_gspace* g, const char* what, LightconeState** out) {
-  if (!g->lightcone || !g->lightcone->has) {
+  if (!g->lightcone || !g->lightcone->ctr.has) {
     set_error("swh_gspace_lightcone_crossings must precede %s", what);
     return SWH_ERR_STATE;
   }
@@ -399,11 +379,8 @@ static swh_status lc_ready(swh_gspace* g, const char* what, LightconeState** out
     return SWH_ERR_STATE;
   }
   SWH_HIP(hipSetDevice(g->ctx->device));
-  if (g->lightcone->pending) {
-    SWH_HIP(hipEventSynchronize(g->lightcone->event));
-    g->lightcone->pending = false;
-  }
-  *out = g->lightcone;
+  SWH_TRY(g->lightcone->ctr.wait());
+  *out = g->lightcone.get();
   return SWH_OK;
 }
 
@@ -425,36 +402,28 @@ swh_status swh_gspace_lightcone_crossings(swh_gspace* g, const swh_lightcone_par
     return SWH_ERR_ARG;
   }
   SWH_HIP(hipSetDevice(g->ctx->device));
-  if (!g->lightcone) g->lightcone = new LightconeState();
+  if (!g->lightcone) g->lightcone = make_owned<LightconeState>();
   LightconeState& F = *g->lightcone;
   hipStream_t st = g->stream;
-  SWH_TRY(F.host.reserve(LC_COUNT * sizeof(unsigned long long)));
-  if (!F.event) SWH_HIP(hipEventCreateWithFlags(&F.event, hipEventDisableTiming));
-  if (F.pending) {  // the pinned buffers are the last call's until it is through
-    SWH_HIP(hipEventSynchronize(F.event));
-    F.pending = false;
-  }
+  SWH_TRY(F.ctr.wait());  // the pinned buffers are the last call's until it is through
   F.n = g->n;
   F.capacity = P.capacity;
-  if (g->n == 0 || P.nrep == 0) {  // nothing to test: zero counts, nothing queued
-    std::memset(F.host.ptr, 0, LC_COUNT * sizeof(unsigned long long));
-    F.has = true;
-    return SWH_OK;
-  }
-  F.has = false;
+  if (g->n == 0 || P.nrep == 0)  // nothing to test: zero counts, nothing queued
+    return F.ctr.set_host(nullptr, LC_COUNT * sizeof(unsigned long long));
+  F.ctr.invalidate();
   const int n = (int)g->n;
   const size_t cap = (size_t)P.capacity, CAP = std::max<size_t>(1, cap);
   const size_t rep_bytes = (size_t)P.nrep * sizeof(LightconeRep);
   SWH_TRY(F.reps.reserve(rep_bytes));
   SWH_TRY(F.host_reps.reserve(rep_bytes));
-  SWH_TRY(F.ctr.reserve(LC_COUNT * sizeof(unsigned long long)));
+  SWH_TRY(F.ctr.prepare(LC_COUNT * sizeof(unsigned long long)));
   SWH_TRY(F.rec.reserve(CAP * sizeof(swh_lightcone_record)));
   SWH_TRY(F.rec2.reserve(CAP * sizeof(swh_lightcone_record)));
   SWH_TRY(F.key.reserve(CAP * 8));
   SWH_TRY(F.key2.reserve(CAP * 8));
   SWH_TRY(F.idx.reserve(CAP * 4));
   SWH_TRY(F.idx2.reserve(CAP * 4));
-  unsigned long long* ctr = F.ctr.as<unsigned long long>();
+  unsigned long long* ctr = F.ctr.dev<unsigned long long>();
   const unsigned long long sentinel = (unsigned long long)(unsigned int)n << P.key_shift;
   const int fill_grid = (int)std::min<size_t>(2048, (CAP + 255) / 256);
 
@@ -492,18 +461,14 @@ swh_status swh_gspace_lightcone_crossings(swh_gspace* g, const swh_lightcone_par
     SWH_HIP(hipGetLastError());
   }
   SWH_TRY(F.timer.end(LT_SORT, st));
-  SWH_HIP(hipMemcpyAsync(F.host.ptr, ctr, LC_COUNT * sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost, st));
-  SWH_HIP(hipEventRecord(F.event, st));
-  F.pending = F.has = true;
-  return SWH_OK;
+  return F.ctr.queue(st);
 }
 
 swh_status swh_gspace_lightcone_result(swh_gspace* g, swh_lightcone_result* out) {
   if (!g || !out) return SWH_ERR_ARG;
   LightconeState* F = nullptr;
   SWH_TRY(lc_ready(g, "swh_gspace_lightcone_result", &F));
-  const unsigned long long* h = reinterpret_cast<const unsigned long long*>(F->host.ptr);
+  const unsigned long long* h = F->ctr.host<unsigned long long>();
   out->n_crossings = (int64_t)h[LC_KEPT];
   out->n_stored = (int64_t)h[LC_STORED];
   out->n_slots = (int64_t)h[LC_SLOTS];
@@ -519,7 +484,7 @@ swh_status swh_gspace_lightcone_records(swh_gspace* g, swh_lightcone_record* rec
   LightconeState* F = nullptr;
   SWH_TRY(lc_ready(g, "swh_gspace_lightcone_records", &F));
   const int64_t stored =
-      (int64_t)reinterpret_cast<const unsigned long long*>(F->host.ptr)[LC_STORED];
+      (int64_t)F->ctr.host<unsigned long long>()[LC_STORED];
   if (n < 0 || n > stored) {
     set_error("swh_gspace_lightcone_records: n = %lld, the last pass stored %lld", (long long)n,
               (long long)stored);

@@ -30,7 +30,7 @@ namespace swh {
 
 namespace {
 
-// lim_rec slots (u32): woken active / inactive particles, 127 - min new bin
+// swh_space.lim slots (u32): woken active / inactive particles, 127 - min new bin
 enum { LIM_N_ACTIVE = 0, LIM_N_INACTIVE, LIM_MIN_BIN_C, LIM_SLOTS = 4 };
 
 __global__ void wake_fill_kernel(int* __restrict__ wake, int64_t n) {
@@ -227,25 +227,20 @@ swh_status limiter_apply(swh_space* s, const swh_limiter_params* L, const swh_hy
   SWH_TRY(apply_ready(s, what));
   // no loop since the last apply: every wake-up is still reset, and the step
   // record and the counts of that apply stand as they are
-  if (s->lim_has && !s->wake_dirty) return SWH_OK;
+  if (s->lim.has && !s->wake_dirty) return SWH_OK;
   SWH_HIP(hipSetDevice(s->ctx->device));
   hipStream_t st = s->stream;
   SWH_TRY(space_ensure_xsorted(s));
   SWH_TRY(ensure_wake(s));
-  SWH_TRY(s->lim_rec.reserve(LIM_SLOTS * sizeof(unsigned int)));
-  SWH_TRY(s->lim_host.reserve(LIM_SLOTS * sizeof(unsigned int)));
-  if (!s->lim_event) SWH_HIP(hipEventCreateWithFlags(&s->lim_event, hipEventDisableTiming));
-  SWH_HIP(hipMemsetAsync(s->lim_rec.ptr, 0, LIM_SLOTS * sizeof(unsigned int), st));
+  SWH_TRY(s->lim.prepare(LIM_SLOTS * sizeof(unsigned int)));
+  SWH_HIP(hipMemsetAsync(s->lim.dev<unsigned int>(), 0, LIM_SLOTS * sizeof(unsigned int), st));
   const int grid = (int)std::min<int64_t>((s->n + 255) / 256, 4 * kReduceBlocks);
   const float4* agrav = LK ? s->gp_agrav_s.as<const float4>() : s->agrav_s.as<const float4>();
   hipLaunchKernelGGL((limiter_apply_kernel<LK>), dim3(grid), dim3(256), 0, st, soa_of(s),
                      s->vfull_s.as<float4>(), agrav, s->hasg_s.as<const int8_t>(),
-                     s->wake_s.as<int>(), s->n, K, s->step.dev(), s->lim_rec.as<unsigned int>());
+                     s->wake_s.as<int>(), s->n, K, s->step.dev(), s->lim.dev<unsigned int>());
   SWH_HIP(hipGetLastError());
-  SWH_HIP(hipMemcpyAsync(s->lim_host.ptr, s->lim_rec.ptr, LIM_SLOTS * sizeof(unsigned int),
-                         hipMemcpyDeviceToHost, st));
-  SWH_HIP(hipEventRecord(s->lim_event, st));
-  s->lim_has = true;
+  SWH_TRY(s->lim.queue(st));
   s->wake_dirty = false;
   // the merged step record, as every launch of the step kernel leaves it
   SWH_TRY(s->step.readback(st));
@@ -269,15 +264,6 @@ swh_status space_wakeup_to_caller(swh_space* s) {
   s->wake_sorted = false;
   s->wake_caller = true;
   return SWH_OK;
-}
-
-void limiter_release(swh_space* s) {
-  s->wake_s.release();
-  s->wake_c.release();
-  s->lim_rec.release();
-  s->lim_host.release();
-  if (s->lim_event) (void)hipEventDestroy(s->lim_event);
-  s->lim_event = nullptr;
 }
 
 }  // namespace swh
@@ -392,14 +378,14 @@ swh_status swh_space_limiter_result(swh_space* s, swh_limiter_result* out) {
   out->min_new_bin = SWH_NUM_TIME_BINS + 1;
   out->reserved = 0;
   if (s->n == 0) return SWH_OK;
-  if (!s->lim_has) {
+  if (!s->lim.has) {
     set_error("swh_space_limiter_apply or swh_space_end_step_limited must precede "
               "swh_space_limiter_result");
     return SWH_ERR_STATE;
   }
   SWH_HIP(hipSetDevice(s->ctx->device));
-  SWH_HIP(hipEventSynchronize(s->lim_event));
-  const unsigned int* h = static_cast<const unsigned int*>(s->lim_host.ptr);
+  SWH_TRY(s->lim.wait());
+  const unsigned int* h = s->lim.host<unsigned int>();
   out->n_woken_active = (int64_t)h[LIM_N_ACTIVE];
   out->n_woken_inactive = (int64_t)h[LIM_N_INACTIVE];
   if (h[LIM_N_ACTIVE] + h[LIM_N_INACTIVE] > 0) out->min_new_bin = 127 - (int32_t)h[LIM_MIN_BIN_C];

@@ -167,16 +167,10 @@ __global__ void mesh_accel_kernel(GLayout L, char* __restrict__ aos, int64_t n, 
   *reinterpret_cast<float*>(r + off_pot_mesh) = pm;
 }
 
-void mesh_release(swh_gspace* g) {
-  g->mesh_rho.release();
-  g->mesh_frho.release();
-  if (g->mesh_plans_valid) {
-    hipfftDestroy((hipfftHandle)g->mesh_fwd);
-    hipfftDestroy((hipfftHandle)g->mesh_inv);
-  }
-  g->mesh_plans_valid = false;
-  g->mesh_N = 0;
-}
+using FftPlan = Handle<hipfftHandle, hipfftDestroy>;
+struct MeshPlans {
+  FftPlan fwd, inv;  // D2Z, Z2D of side swh_gspace.mesh_N
+};
 
 }  // namespace swh
 
@@ -204,32 +198,25 @@ swh_status swh_gspace_pm_mesh(swh_gspace* g, const swh_pm_params* M, double* pot
   SWH_TRY(g->mesh_rho.reserve(N3 * sizeof(double)));
   SWH_TRY(g->mesh_frho.reserve(NC * sizeof(hipfftDoubleComplex)));
   if (g->mesh_N != N) {
-    if (g->mesh_plans_valid) {
-      hipfftDestroy((hipfftHandle)g->mesh_fwd);
-      hipfftDestroy((hipfftHandle)g->mesh_inv);
-      g->mesh_plans_valid = false;
-    }
-    hipfftHandle f = nullptr, b = nullptr;
+    g->mesh_N = 0;
+    g->mesh_plans = make_owned<MeshPlans>();  // (the plans of another side go)
+    MeshPlans& P = *g->mesh_plans;
     size_t wf = 0, wb = 0;
-    hipfftResult rf = hipfftCreate(&f);
-    if (rf == HIPFFT_SUCCESS) rf = hipfftMakePlan3d(f, N, N, N, HIPFFT_D2Z, &wf);
-    hipfftResult rb = rf == HIPFFT_SUCCESS ? hipfftCreate(&b) : rf;
-    if (rb == HIPFFT_SUCCESS) rb = hipfftMakePlan3d(b, N, N, N, HIPFFT_Z2D, &wb);
+    hipfftResult rf = hipfftCreate(P.fwd.put());
+    if (rf == HIPFFT_SUCCESS) rf = hipfftMakePlan3d(P.fwd, N, N, N, HIPFFT_D2Z, &wf);
+    hipfftResult rb = rf == HIPFFT_SUCCESS ? hipfftCreate(P.inv.put()) : rf;
+    if (rb == HIPFFT_SUCCESS) rb = hipfftMakePlan3d(P.inv, N, N, N, HIPFFT_Z2D, &wb);
     if (std::getenv("SWH_PM_DEBUG"))
       std::fprintf(stderr, "swh_gspace_pm_mesh: N = %d D2Z plan %d work %zu B, Z2D plan %d work %zu B\n",
                    N, (int)rf, wf, (int)rb, wb);
     if (rf != HIPFFT_SUCCESS || rb != HIPFFT_SUCCESS) {
-      if (f) hipfftDestroy(f);
-      if (b) hipfftDestroy(b);
+      g->mesh_plans.reset();
       set_error("hipfftMakePlan3d failed for N = %d (D2Z %d, Z2D %d)", N, (int)rf, (int)rb);
       return SWH_ERR_HIP;
     }
-    g->mesh_fwd = (void*)f;
-    g->mesh_inv = (void*)b;
-    g->mesh_plans_valid = true;
     g->mesh_N = N;
   }
-  hipfftHandle f = (hipfftHandle)g->mesh_fwd, b = (hipfftHandle)g->mesh_inv;
+  const hipfftHandle f = g->mesh_plans->fwd, b = g->mesh_plans->inv;
   if (hipfftSetStream(f, g->stream) != HIPFFT_SUCCESS ||
       hipfftSetStream(b, g->stream) != HIPFFT_SUCCESS)
     return SWH_ERR_HIP;

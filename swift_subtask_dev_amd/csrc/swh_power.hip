@@ -55,7 +55,7 @@ constexpr int kPowShotBlocks = 256;  // the shot noise's, as kStatsBlocks
 constexpr int kPowShotSlots = 4;     // per spectrum: shot sum, n in field 1, in field 2, n_nonfinite
 
 struct PowPlan {
-  hipfftHandle fwd = nullptr;
+  Handle<hipfftHandle, hipfftDestroy> fwd;
   DevBuf invsinc;  // double[N]: power_invsinc of every index
 };
 
@@ -63,28 +63,22 @@ struct PowerState {
   DevBuf rho;                 // double[N^3]: the grid being assigned
   DevBuf fgrid[kPowTypes];    // its transform, one per distinct type of the call
   DevBuf bin_part, shot_part; // the blocks' partial records
-  DevBuf out;                 // the results, 8 bytes a slot
-  HostBuf host;
+  Readback out;               // the results, 8 bytes a slot
   std::map<int, PowPlan> plans;  // by N
-  hipEvent_t event = nullptr;
-  bool has = false, pending = false;
   int n_spectra = 0, n_folds = 0, nbins = 0;
   // HIP events around every piece of a stage; a stage's time is their sum
   struct Piece {
     int stage;
-    hipEvent_t ev[2];
+    Event ev[2];
   };
   std::vector<Piece> pieces;
   size_t used = 0;
   swh_status begin(int stage, hipStream_t st) {
-    if (used == pieces.size()) {
-      Piece p{stage, {nullptr, nullptr}};
-      SWH_HIP(hipEventCreate(&p.ev[0]));
-      SWH_HIP(hipEventCreate(&p.ev[1]));
-      pieces.push_back(p);
-    }
-    pieces[used].stage = stage;
-    SWH_HIP(hipEventRecord(pieces[used].ev[0], st));
+    if (used == pieces.size()) pieces.emplace_back();
+    Piece& p = pieces[used];
+    for (Event& e : p.ev) SWH_TRY(e.ensure());
+    p.stage = stage;
+    SWH_HIP(hipEventRecord(p.ev[0], st));
     return SWH_OK;
   }
   swh_status end(hipStream_t st) {
@@ -92,35 +86,7 @@ struct PowerState {
     used++;
     return SWH_OK;
   }
-  void release() {
-    rho.release();
-    for (DevBuf& b : fgrid) b.release();
-    bin_part.release();
-    shot_part.release();
-    out.release();
-    host.release();
-    for (auto& kv : plans) {
-      if (kv.second.fwd) hipfftDestroy(kv.second.fwd);
-      kv.second.invsinc.release();
-    }
-    plans.clear();
-    if (event) (void)hipEventDestroy(event);
-    event = nullptr;
-    for (Piece& p : pieces)
-      for (hipEvent_t& e : p.ev)
-        if (e) (void)hipEventDestroy(e);
-    pieces.clear();
-    used = 0;
-    has = pending = false;
-  }
 };
-
-void power_release(swh_gspace* g) {
-  if (!g->power) return;
-  g->power->release();
-  delete g->power;
-  g->power = nullptr;
-}
 
 // One gpart's position, mass, bin and type (1 without a step layout: only
 // `matter` is asked then, and it reads no type).
@@ -319,20 +285,15 @@ static int pow_bin_blocks(int N) {
 static swh_status pow_plan(PowerState& S, int N, hipStream_t st, PowPlan** out) {
   auto it = S.plans.find(N);
   if (it == S.plans.end()) {
-    PowPlan P;
+    PowPlan P;  // (an early return frees what it holds)
     size_t work = 0;
-    hipfftResult r = hipfftCreate(&P.fwd);
+    hipfftResult r = hipfftCreate(P.fwd.put());
     if (r == HIPFFT_SUCCESS) r = hipfftMakePlan3d(P.fwd, N, N, N, HIPFFT_D2Z, &work);
     if (r != HIPFFT_SUCCESS) {
-      if (P.fwd) hipfftDestroy(P.fwd);
       set_error("swh_gspace_power_spectrum: hipfftMakePlan3d failed for N = %d (D2Z %d)", N, (int)r);
       return SWH_ERR_HIP;
     }
-    swh_status s = P.invsinc.reserve((size_t)N * sizeof(double));
-    if (s != SWH_OK) {
-      hipfftDestroy(P.fwd);
-      return s;
-    }
+    SWH_TRY(P.invsinc.reserve((size_t)N * sizeof(double)));
     std::vector<double> t((size_t)N);
     for (int i = 0; i < N; i++) t[(size_t)i] = power_invsinc(i, N);
     // (pageable source: the copy has left `t` when the call returns)
@@ -340,12 +301,10 @@ static swh_status pow_plan(PowerState& S, int N, hipStream_t st, PowPlan** out) 
                                   hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
-      hipfftDestroy(P.fwd);
-      P.invsinc.release();
       set_error("swh_gspace_power_spectrum: the table's upload failed: %s", hipGetErrorString(e));
       return SWH_ERR_HIP;
     }
-    it = S.plans.emplace(N, P).first;
+    it = S.plans.emplace(N, std::move(P)).first;
   }
   if (hipfftSetStream(it->second.fwd, st) != HIPFFT_SUCCESS) {
     set_error("swh_gspace_power_spectrum: hipfftSetStream failed");
@@ -419,15 +378,11 @@ swh_status swh_gspace_power_spectrum(swh_gspace* g, const swh_power_params* P) {
     SWH_TRY(grec_require(L, GF_X | GF_MASS | GF_TIME_BIN | (g->step_layout_set ? GF_TYPE : 0u),
                          "swh_gspace_power_spectrum"));
   SWH_HIP(hipSetDevice(g->ctx->device));
-  if (!g->power) g->power = new PowerState();
+  if (!g->power) g->power = make_owned<PowerState>();
   PowerState& S = *g->power;
   hipStream_t st = g->stream;
-  if (!S.event) SWH_HIP(hipEventCreateWithFlags(&S.event, hipEventDisableTiming));
-  if (S.pending) {
-    SWH_HIP(hipEventSynchronize(S.event));
-    S.pending = false;
-  }
-  S.has = false;
+  SWH_TRY(S.out.wait());  // the pinned results are the last call's until it is through
+  S.out.invalidate();
   const int N = P->N, nz = N / 2 + 1, nf = P->n_folds, ns = P->n_spectra, order = P->window_order;
   const size_t N3 = (size_t)N * N * N, NC = (size_t)N * N * nz;
   const size_t slots = (size_t)ns * nf * 2 * nz + (size_t)ns * kPowShotSlots;
@@ -439,12 +394,11 @@ swh_status swh_gspace_power_spectrum(swh_gspace* g, const swh_power_params* P) {
     if (used[t]) SWH_TRY(S.fgrid[t].reserve(NC * sizeof(double2)));
   SWH_TRY(S.bin_part.reserve((size_t)bin_blocks * 2 * nz * sizeof(double)));
   SWH_TRY(S.shot_part.reserve((size_t)shot_blocks * kPowShotSlots * sizeof(double)));
-  SWH_TRY(S.out.reserve(slots * sizeof(double)));
-  SWH_TRY(S.host.reserve(slots * sizeof(double)));
+  SWH_TRY(S.out.prepare(slots * sizeof(double)));
   PowPlan* plan = nullptr;
   SWH_TRY(pow_plan(S, N, st, &plan));
   S.used = 0;
-  double* out = S.out.as<double>();
+  double* out = S.out.dev<double>();
   double* shot_out = out + (size_t)ns * nf * 2 * nz;
 
   // the shot noise and the counts, per pair, in the unfolded box
@@ -499,11 +453,8 @@ swh_status swh_gspace_power_spectrum(swh_gspace* g, const swh_power_params* P) {
     SWH_TRY(S.end(st));
     dim /= P->fold_factor;  // fold the box (:1195)
   }
-  SWH_HIP(hipMemcpyAsync(S.host.ptr, S.out.ptr, slots * sizeof(double), hipMemcpyDeviceToHost, st));
-  SWH_HIP(hipEventRecord(S.event, st));
   S.n_spectra = ns, S.n_folds = nf, S.nbins = nz;
-  S.pending = S.has = true;
-  return SWH_OK;
+  return S.out.queue(st);
 }
 
 swh_status swh_gspace_power_spectrum_result(swh_gspace* g, int32_t n_spectra, int32_t n_folds,
@@ -511,8 +462,8 @@ swh_status swh_gspace_power_spectrum_result(swh_gspace* g, int32_t n_spectra, in
                                             double* shot_sum, int64_t* n_contributing,
                                             int64_t* n_nonfinite) {
   if (!g) return SWH_ERR_ARG;
-  PowerState* S = g->power;
-  if (!S || !S->has) {
+  PowerState* S = g->power.get();
+  if (!S || !S->out.has) {
     set_error("swh_gspace_power_spectrum must precede swh_gspace_power_spectrum_result");
     return SWH_ERR_STATE;
   }
@@ -522,12 +473,9 @@ swh_status swh_gspace_power_spectrum_result(swh_gspace* g, int32_t n_spectra, in
     return SWH_ERR_ARG;
   }
   SWH_HIP(hipSetDevice(g->ctx->device));
-  if (S->pending) {
-    SWH_HIP(hipEventSynchronize(S->event));
-    S->pending = false;
-  }
+  SWH_TRY(S->out.wait());
   const int nz = S->nbins;
-  const double* h = reinterpret_cast<const double*>(S->host.ptr);
+  const double* h = S->out.host<double>();
   const size_t rows = (size_t)S->n_spectra * S->n_folds;
   for (size_t r = 0; r < rows; r++) {
     if (powersum) std::memcpy(powersum + r * nz, h + r * 2 * nz, (size_t)nz * 8);
@@ -545,8 +493,8 @@ swh_status swh_gspace_power_spectrum_result(swh_gspace* g, int32_t n_spectra, in
 
 swh_status swh_gspace_power_spectrum_times(swh_gspace* g, float* ms) {
   if (!g || !ms) return SWH_ERR_ARG;
-  PowerState* S = g->power;
-  if (!S || !S->has) {
+  PowerState* S = g->power.get();
+  if (!S || !S->out.has) {
     set_error("swh_gspace_power_spectrum must precede swh_gspace_power_spectrum_times");
     return SWH_ERR_STATE;
   }

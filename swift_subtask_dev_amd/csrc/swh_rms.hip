@@ -143,46 +143,31 @@ static int rms_grid(int64_t n) {
 
 static swh_status rms_prepare(RmsState& S, int grid) {
   SWH_TRY(S.partials.reserve((size_t)grid * sizeof(swh_displacement_sums)));
-  SWH_TRY(S.out.reserve(sizeof(swh_displacement_sums)));
-  SWH_TRY(S.host.reserve(sizeof(swh_displacement_sums)));
-  if (!S.event) SWH_HIP(hipEventCreateWithFlags(&S.event, hipEventDisableTiming));
-  return SWH_OK;
+  return S.rb.prepare(sizeof(swh_displacement_sums));
 }
 
 // after the blocks' launch: the one-wave reduction and the copy behind it
 static swh_status rms_finish(RmsState& S, int grid, hipStream_t st) {
   hipLaunchKernelGGL(rms_reduce_kernel, dim3(1), dim3(64), 0, st,
                      S.partials.as<const swh_displacement_sums>(), grid,
-                     S.out.as<swh_displacement_sums>());
+                     S.rb.dev<swh_displacement_sums>());
   SWH_HIP(hipGetLastError());
-  SWH_HIP(hipMemcpyAsync(S.host.ptr, S.out.ptr, sizeof(swh_displacement_sums),
-                         hipMemcpyDeviceToHost, st));
-  SWH_HIP(hipEventRecord(S.event, st));
-  S.pending = S.has = true;
-  return SWH_OK;
+  return S.rb.queue(st);
 }
 
 // an empty set: nothing counted, nothing queued
 static swh_status rms_empty(RmsState& S) {
-  if (S.pending) SWH_HIP(hipEventSynchronize(S.event));
-  SWH_TRY(S.host.reserve(sizeof(swh_displacement_sums)));
   const swh_displacement_sums none{0., FLT_MAX, 0, 0};
-  std::memcpy(S.host.ptr, &none, sizeof(none));
-  S.pending = false;
-  S.has = true;
-  return SWH_OK;
+  return S.rb.set_host(&none, sizeof(none));
 }
 
 static swh_status rms_result(RmsState& S, swh_displacement_sums* out, const char* entry) {
-  if (!S.has) {
+  if (!S.rb.has) {
     set_error("%s must precede %s_result", entry, entry);
     return SWH_ERR_STATE;
   }
-  if (S.pending) {
-    SWH_HIP(hipEventSynchronize(S.event));
-    S.pending = false;
-  }
-  std::memcpy(out, S.host.ptr, sizeof(swh_displacement_sums));
+  SWH_TRY(S.rb.wait());
+  std::memcpy(out, S.rb.host<swh_displacement_sums>(), sizeof(swh_displacement_sums));
   return SWH_OK;
 }
 

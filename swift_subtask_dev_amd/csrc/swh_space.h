@@ -116,7 +116,6 @@ swh_status space_kick1_linked(swh_space* s, const swh_kick_params* K1, const swh
 swh_status space_limiter_walk(swh_space* s, const swh_hydro_params* P);
 // swh_limiter.hip: the wake-up words before / after a re-sort (swh_space_rebuild)
 swh_status space_wakeup_to_caller(swh_space* s);
-void limiter_release(swh_space* s);
 // Recompute max h over the set into the device slot counters[2] (float bits).
 swh_status space_hmax_to_device(swh_space* s);
 

@@ -730,7 +730,8 @@ swh_status swh_space_create(swh_context* ctx, swh_space** out) {
   SWH_HIP(hipSetDevice(ctx->device));
   auto* s = new swh_space();
   s->ctx = ctx;
-  hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+  hipError_t e = hipStreamCreateWithFlags(s->owned_stream.put(), hipStreamNonBlocking);
+  s->stream = s->owned_stream;
   if (e != hipSuccess) {
     delete s;
     set_error("hipStreamCreate failed: %s", hipGetErrorString(e));
@@ -745,24 +746,8 @@ swh_status swh_space_destroy(swh_space* s) {
   if (!s) return SWH_OK;
   (void)hipSetDevice(s->ctx->device);
   (void)hipStreamSynchronize(s->stream);
-  DevBuf* bufs[] = {&s->aos, &s->pos, &s->vm, &s->th, &s->fc, &s->tb, &s->dens, &s->rot,
-                    &s->grad, &s->acc, &s->hdt, &s->mintb, &s->perm, &s->ncount,
-                    &s->cell_start, &s->cell_rank, &s->cell_code, &s->cell_span, &s->cell_hreach,
-                    &s->vfull_c, &s->agrav_c, &s->hasg_c, &s->xdiff, &s->pcell, &s->cell_lin, &s->groups, &s->seg_groups,
-                    &s->seg_off, &s->keys, &s->keys2, &s->idx, &s->idx2, &s->sort_tmp,
-                    &s->scan_tmp, &s->counters, &s->tmp_soa, &s->ghost_left,
-                    &s->ghost_right, &s->ghost_list, &s->ghost_list2, &s->ghost_search, &s->ghost_seg, &s->grown_q,
-                    &s->grown_mark, &s->grown_search,
-                    &s->nbr, &s->nbr_cnt, &s->nbr_base, &s->nbr_reach, &s->nbr_ovf, &s->posf, &s->gplan, &s->ctr_stripes,
-                    &s->iperm, &s->vfull_s, &s->agrav_s, &s->hasg_s, &s->list_xd0};
-  for (DevBuf* b : bufs) b->release();
-  couple_release(s);
-  limiter_release(s);
-  s->step.release();
-  s->hstage.release();
-  s->ghost_host.release();
-  if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
+  couple_unlink(s);
+  delete s;  // every member frees what it owns, the owned stream last
   return SWH_OK;
 }
 
@@ -770,12 +755,11 @@ swh_status swh_space_set_stream(swh_space* s, void* stream) {
   SWH_TRY(swh::space_apply_pending(s));
   if (!s) return SWH_ERR_ARG;
   if (stream) {
-    if (s->own_stream && s->stream) {
-      (void)hipStreamSynchronize(s->stream);
-      (void)hipStreamDestroy(s->stream);
+    if (s->owned_stream) {
+      (void)hipStreamSynchronize(s->owned_stream);
+      s->owned_stream.reset();
     }
     s->stream = reinterpret_cast<hipStream_t>(stream);
-    s->own_stream = false;
   }
   return SWH_OK;
 }
@@ -960,7 +944,7 @@ swh_status swh_space_upload_parts(swh_space* s, const void* parts, int64_t count
   s->xsorted_valid = false;
   s->step.invalidate();
   s->wake_sorted = s->wake_caller = false;  // every particle starts not awake
-  s->lim_has = false;
+  s->lim.invalidate();
   s->wake_dirty = false;
   s->grid.dx = 0.;
   hipLaunchKernelGGL(unpack_kernel, dim3(grid), dim3(block), 0, s->stream, L,

@@ -262,45 +262,28 @@ static swh_status fill_stats(const swh_stats_params* P, const char* what, StatsD
 
 static swh_status stats_prepare(StatsState& S, int grid) {
   SWH_TRY(S.partials.reserve((size_t)grid * ST_SLOTS * sizeof(double)));
-  SWH_TRY(S.out.reserve(ST_SLOTS * sizeof(double)));
-  SWH_TRY(S.host.reserve(sizeof(swh_statistics)));
-  if (!S.event) SWH_HIP(hipEventCreateWithFlags(&S.event, hipEventDisableTiming));
-  return SWH_OK;
+  return S.rb.prepare(sizeof(swh_statistics));
 }
 
 // after the blocks' launch: the one-wave reduction and the copy behind it
 static swh_status stats_finish(StatsState& S, int grid, hipStream_t st) {
   hipLaunchKernelGGL(stats_reduce_kernel, dim3(1), dim3(64), 0, st,
-                     S.partials.as<const double>(), grid, S.out.as<double>());
+                     S.partials.as<const double>(), grid, S.rb.dev<double>());
   SWH_HIP(hipGetLastError());
   SWH_TRY(S.timer.end(ST_T_STATS, st));
-  SWH_HIP(hipMemcpyAsync(S.host.ptr, S.out.ptr, sizeof(swh_statistics), hipMemcpyDeviceToHost,
-                         st));
-  SWH_HIP(hipEventRecord(S.event, st));
-  S.pending = S.has = true;
-  return SWH_OK;
+  return S.rb.queue(st);
 }
 
 // an empty set: zeros, nothing queued
-static swh_status stats_zero(StatsState& S) {
-  if (S.pending) SWH_HIP(hipEventSynchronize(S.event));
-  SWH_TRY(S.host.reserve(sizeof(swh_statistics)));
-  std::memset(S.host.ptr, 0, sizeof(swh_statistics));
-  S.pending = false;
-  S.has = true;
-  return SWH_OK;
-}
+static swh_status stats_zero(StatsState& S) { return S.rb.set_host(nullptr, sizeof(swh_statistics)); }
 
 static swh_status stats_result(StatsState& S, swh_statistics* out, const char* entry) {
-  if (!S.has) {
+  if (!S.rb.has) {
     set_error("%s must precede %s_result", entry, entry);
     return SWH_ERR_STATE;
   }
-  if (S.pending) {
-    SWH_HIP(hipEventSynchronize(S.event));
-    S.pending = false;
-  }
-  std::memcpy(out, S.host.ptr, sizeof(swh_statistics));
+  SWH_TRY(S.rb.wait());
+  std::memcpy(out, S.rb.host<swh_statistics>(), sizeof(swh_statistics));
   return SWH_OK;
 }
 

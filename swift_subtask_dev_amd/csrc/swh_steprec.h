@@ -5,7 +5,7 @@
 // commit: per wave by shuffles, per block through LDS, then one integer atomic
 // per block and field, so the record does not depend on the order of the
 // blocks. The host side is StepRecord (declared in swh_internal.h, where the
-// spaces hold one): the buffers, the copy to the host and its decoding.
+// spaces hold one): the slots' memsets, the readback and its decoding.
 // Nothing here is floating-point arithmetic (max, compare and integer
 // operations only), so a translation unit's fp contraction cannot change it.
 #pragma once
@@ -128,38 +128,25 @@ struct StepRecLane {
 
 inline swh_status StepRecord::prepare(hipStream_t st, bool ts) {
   const size_t bytes = rec_slots(stride) * sizeof(unsigned long long);
-  SWH_TRY(host.reserve(bytes));
-  if (!rec.ptr) {
-    SWH_TRY(rec.reserve(bytes));
-    SWH_HIP(hipMemsetAsync(rec.ptr, 0, bytes, st));
-  }
-  if (!event) SWH_HIP(hipEventCreateWithFlags(&event, hipEventDisableTiming));
+  const bool fresh = !rb.rec.ptr;
+  SWH_TRY(rb.prepare(bytes));
+  if (fresh) SWH_HIP(hipMemsetAsync(rb.rec.ptr, 0, bytes, st));
   const size_t slot = (size_t)stride * sizeof(unsigned long long);
   if (ts) SWH_HIP(hipMemsetAsync(dev(), 0, REC_VMAX * slot, st));
   SWH_HIP(hipMemsetAsync(dev() + REC_VMAX * stride, 0, sizeof(unsigned long long), st));
   return SWH_OK;
 }
 
-inline swh_status StepRecord::readback(hipStream_t st) {
-  SWH_HIP(hipMemcpyAsync(host.ptr, rec.ptr, rec_slots(stride) * sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost, st));
-  SWH_HIP(hipEventRecord(event, st));
-  pending = true;
-  return SWH_OK;
-}
-
 inline swh_status StepRecord::fetch() {
-  if (!pending) return SWH_OK;
-  SWH_HIP(hipEventSynchronize(event));
-  pending = false;
-  const unsigned int vb =
-      (unsigned int)static_cast<const unsigned long long*>(host.ptr)[REC_VMAX * stride];
+  if (!rb.pending) return SWH_OK;
+  SWH_TRY(rb.wait());
+  const unsigned int vb = (unsigned int)rb.host<unsigned long long>()[REC_VMAX * stride];
   std::memcpy(&vmax, &vb, sizeof(vmax));
   return SWH_OK;
 }
 
 inline swh_status StepRecord::decode(swh_step_result* out, const char* noun) const {
-  const unsigned long long* h = static_cast<const unsigned long long*>(host.ptr);
+  const unsigned long long* h = rb.host<unsigned long long>();
   out->ti_end_min = kMaxNrTimesteps - (int64_t)h[REC_END_MIN * stride];
   out->ti_end_max = (int64_t)h[REC_END_MAX * stride];
   out->ti_beg_max = (int64_t)h[REC_BEG_MAX * stride];
@@ -173,14 +160,6 @@ inline swh_status StepRecord::decode(swh_step_result* out, const char* noun) con
     return SWH_ERR_ARG;
   }
   return SWH_OK;
-}
-
-inline void StepRecord::release() {
-  rec.release();
-  host.release();
-  if (event) (void)hipEventDestroy(event);
-  event = nullptr;
-  invalidate();
 }
 
 }  // namespace swh
