@@ -1344,10 +1344,13 @@ SWH_API swh_status swh_gspace_power_spectrum_times(swh_gspace *g, float *ms);
 /* list; a copy crosses when its r2 at the start of the drift is at    */
 /* most R_start^2 and its r2 at the end at least R_end^2, all in fp64  */
 /* in the reference's operation order without fused multiply-adds.     */
-/* Not covered: the HEALPix maps, the gas, star, sink and black-hole   */
-/* property fields and their output filters, the HDF5 writer,          */
-/* lightcones across ranks. Nothing here writes a record, the tree or  */
-/* a multipole, marks the tree stale or needs a tree.                  */
+/* Not covered: the gas, star, sink and black-hole property fields and */
+/* their output filters, the HDF5 writer, lightcones across ranks; of  */
+/* the HEALPix maps (below): the SPH-smoothed maps, the gas-property   */
+/* and x-ray maps, StarFormationRate, the neutrino baseline and        */
+/* delta-f weight, shell completion and freeing, maps split across     */
+/* ranks, restart state. Nothing here writes a record, the tree or a   */
+/* multipole, marks the tree stale or needs a tree.                    */
 /* ------------------------------------------------------------------ */
 #define SWH_LIGHTCONE_TYPES 7 /* swift_type_count */
 typedef struct swh_lightcone_replication { /* struct replication */
@@ -1415,6 +1418,79 @@ SWH_API swh_status swh_gspace_lightcone_records(swh_gspace *g, swh_lightcone_rec
  * events on the gspace's stream; waits for them): ms[0..2) = the pass (list
  * copy, cull, tests, append), the sort. -1 before any call. */
 SWH_API swh_status swh_gspace_lightcone_times(swh_gspace *g, float *ms);
+
+/* ------------------------------------------------------------------ */
+/* HEALPix mass maps of lightcone shells (added to ABI v15; purely     */
+/* additive): SWIFT's lightcone_buffer_map_update and the point branch */
+/* of healpix_smoothing_mapper (src/lightcone/lightcone.c:1557,        */
+/* lightcone_shell.c:646) for one lightcone. The crossing pass above   */
+/* with a second sink: a crossing is a direction and a float mass, and */
+/* each is added straight into pixel arrays (RING scheme, fp64) that   */
+/* stay on the device from open to close; no record is written,        */
+/* nothing is sorted, nothing is downloaded per step. The pixel comes  */
+/* from the angles of x_cross after the quantisation of the            */
+/* reference's update buffer (30-bit steps of pi). A crossing is in    */
+/* shell s when r_min[s] <= |x_cross| < r_max[s] (the reference asks   */
+/* amin < a_cross <= amax on its interpolated a_cross: the same set    */
+/* for r_min = R(amax), r_max = R(amin) up to that table's error), and */
+/* shells that overlap each get it. A map is a mask of particle types  */
+/* (bit t: swift_type t); every particle is added as a point with its  */
+/* gpart mass. The sums are fp64 atomic adds: their last bits depend   */
+/* on the arrival order; every counter is exact and reproducible.      */
+/* Not covered: see the list above.                                    */
+/* ------------------------------------------------------------------ */
+#define SWH_LIGHTCONE_MAX_MAPS 8
+#define SWH_LIGHTCONE_MAX_NSIDE 8192
+#define SWH_LIGHTCONE_MAX_STEP_SHELLS 64
+/* the type masks of the reference's mass maps (lightcone_map_types.c) */
+#define SWH_MAP_TOTAL_MASS 0x77u          /* gas, DM, DM background, stars, BH, neutrino */
+#define SWH_MAP_DARK_MATTER_MASS 0x06u
+#define SWH_MAP_UNSMOOTHED_GAS_MASS 0x01u
+#define SWH_MAP_STELLAR_MASS 0x10u
+#define SWH_MAP_BLACK_HOLE_MASS 0x20u
+typedef struct swh_lightcone_maps_result {
+  int64_t n_crossings;  /* crossings of gparts whose type is in some map's mask (last call) */
+  int64_t n_updates;    /* atomic adds of the last call, over shells and maps */
+  int64_t n_no_shell;   /* of the crossings, those in no shell of the step */
+  int64_t n_bad_f;      /* as swh_lightcone_result */
+  int64_t n_pair_tests;
+  int64_t n_tile_tests;
+  int64_t n_tile_kept;
+} swh_lightcone_maps_result;
+/* Allocates n_shells x n_maps x 12 nside^2 zeroed doubles on the gspace; they
+ * persist across accumulate calls, drifts, tree builds and uploads until
+ * _close, swh_gspace_destroy or the next _open, which replaces the set.
+ * SWH_ERR_ARG unless 1 <= nside <= 8192 (any integer), 1 <= n_maps <= 8,
+ * n_shells >= 1, 0 <= r_min[s] < r_max[s] all finite, and every mask names
+ * some of the SWH_LIGHTCONE_TYPES types and nothing else. SWH_ERR_OOM when the
+ * arrays do not fit. After any refusal no set is open: the earlier one is
+ * freed before the new one is looked at. */
+SWH_API swh_status swh_gspace_lightcone_maps_open(swh_gspace *g, int32_t nside, int32_t n_shells,
+                                                  const double *r_min, const double *r_max,
+                                                  int32_t n_maps, const uint32_t *type_mask);
+/* One step's crossings into the maps; call it before the drift, with the
+ * parameters of swh_gspace_lightcone_crossings. capacity, use_type, r2_min and
+ * r2_max are ignored: a gpart is tested when some map's mask has its type.
+ * Only enqueues. The shells looked at are those that meet [R_end - (R_start -
+ * R_end), R_start], at most SWH_LIGHTCONE_MAX_STEP_SHELLS of them (else
+ * SWH_ERR_ARG). The same refusals as swh_gspace_lightcone_crossings, and
+ * SWH_ERR_STATE before _open. An empty set or list queues nothing. */
+SWH_API swh_status swh_gspace_lightcone_maps_accumulate(swh_gspace *g,
+                                                        const swh_lightcone_params *P);
+/* Waits for the last accumulate: its counters (zeros before any), and in
+ * updates[n_shells * n_maps] (may be NULL) the adds per (shell, map) since
+ * _open. */
+SWH_API swh_status swh_gspace_lightcone_maps_result(swh_gspace *g, swh_lightcone_maps_result *out,
+                                                    int64_t *updates);
+/* One map, 12 nside^2 doubles in RING order, as it stands after everything
+ * queued so far. */
+SWH_API swh_status swh_gspace_lightcone_maps_read(swh_gspace *g, int32_t shell, int32_t map,
+                                                  double *out);
+/* Device time of the last accumulate (ms, HIP events; waits): ms[0] = the list
+ * copy, the pass and the copy of the counts. -1 before any. */
+SWH_API swh_status swh_gspace_lightcone_maps_times(swh_gspace *g, float *ms);
+/* Frees the set; nothing happens without one. */
+SWH_API swh_status swh_gspace_lightcone_maps_close(swh_gspace *g);
 
 #ifdef __cplusplus
 }

@@ -624,6 +624,26 @@ class LightconeResult(C.Structure):
         return {n: int(getattr(self, n)) for n in LIGHTCONE_RESULT_FIELDS}
 
 
+# swh_lightcone_maps_*: the reference's mass maps as masks of particle types
+# (bit t: swift_type t; lightcone_map_types.c)
+LIGHTCONE_MAP_MASKS = {"TotalMass": 0x77, "DarkMatterMass": 0x06, "UnsmoothedGasMass": 0x01,
+                       "StellarMass": 0x10, "BlackHoleMass": 0x20}
+LIGHTCONE_MAX_MAPS = 8           # SWH_LIGHTCONE_MAX_MAPS
+LIGHTCONE_MAX_NSIDE = 8192       # SWH_LIGHTCONE_MAX_NSIDE
+LIGHTCONE_MAX_STEP_SHELLS = 64   # SWH_LIGHTCONE_MAX_STEP_SHELLS
+LIGHTCONE_MAPS_RESULT_FIELDS = ("n_crossings", "n_updates", "n_no_shell", "n_bad_f",
+                                "n_pair_tests", "n_tile_tests", "n_tile_kept")
+
+
+class LightconeMapsResult(C.Structure):
+    """swh_lightcone_maps_result: the counts of the last map pass."""
+
+    _fields_ = [(n, C.c_int64) for n in LIGHTCONE_MAPS_RESULT_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n in LIGHTCONE_MAPS_RESULT_FIELDS}
+
+
 class GCell(C.Structure):
     """swh_gcell: a tree cell's gpart range, progeny and geometry."""
 

@@ -40,7 +40,7 @@ HIP_HEADERS = ["swh_internal.h", "swh_physics.h", "swh_space.h", "swh_gather.h",
                "swh_list.h", "swh_mpole.h", "swh_timeline.h", "swh_gstep.h", "swh_couple.h",
                "swh_limiter.h", "swh_steprec.h", "swh_stats.h", "swh_rms.h", "swh_fof.h",
                "swh_grec.h", "swh_grav.h", "swh_gwalk.h", "swh_power.h",
-               "swh_lightcone.h", "swh_device.h"]
+               "swh_lightcone.h", "swh_healpix.h", "swh_device.h"]
 
 
 def _hipcc() -> str:

@@ -466,6 +466,89 @@ def lightcone_shell(cosmo: Cosmology, ti_old: int, ti_current: int, observer, bo
     return out
 
 
+# -- HEALPix maps of lightcone shells (csrc/swh_healpix.h) ---------------------
+def healpix_npix(nside: int) -> int:
+    return 12 * int(nside) * int(nside)
+
+
+def ang2pix_ring(nside: int, theta, phi) -> np.ndarray:
+    """The RING-scheme pixel of directions (theta, phi), any integer nside >= 1,
+    as csrc/swh_healpix.h computes it: the equatorial belt for |z| <= 2/3, the
+    polar caps otherwise, with the sin(theta) form of the cap's ring coordinate
+    where |z| > 0.99. For those who bin lightcone records themselves."""
+    ns = np.int64(nside)
+    fn = np.float64(nside)
+    theta = np.atleast_1d(np.asarray(theta, dtype=np.float64))
+    phi = np.atleast_1d(np.asarray(phi, dtype=np.float64))
+    theta, phi = np.broadcast_arrays(theta, phi)
+    z = np.cos(theta)
+    za = np.abs(z)
+    two_pi, half_pi = 2.0 * np.pi, 0.5 * np.pi
+    tt = np.fmod(phi, two_pi)
+    tt = np.where(tt < 0.0, tt + two_pi, tt)
+    tt = tt / half_pi
+    tt = np.where(tt >= 4.0, tt - 4.0, tt)
+    # the belt
+    t1 = fn * (0.5 + tt)
+    t2 = fn * z * 0.75
+    jp = (t1 - t2).astype(np.int64)
+    jm = (t1 + t2).astype(np.int64)
+    ir = ns + 1 + jp - jm
+    kshift = 1 - (ir & 1)
+    ip = (jp + jm - ns + kshift + 1) // 2
+    belt = 2 * ns * (ns - 1) + (ir - 1) * 4 * ns + ip % (4 * ns)
+    # the caps
+    tp = tt - np.trunc(tt)
+    with np.errstate(invalid="ignore"):
+        tmp = np.where(za > 0.99, fn * np.sin(theta) / np.sqrt((1.0 + za) / 3.0),
+                       fn * np.sqrt(3.0 * np.where(za > 1.0, 0.0, 1.0 - za)))
+    cjp = np.trunc(tp * tmp).astype(np.int64)
+    cjm = np.trunc((1.0 - tp) * tmp).astype(np.int64)
+    cir = cjp + cjm + 1
+    cip = np.trunc(tt * cir.astype(np.float64)).astype(np.int64) % (4 * cir)
+    cap = np.where(z > 0.0, 2 * cir * (cir - 1) + cip, 12 * ns * ns - 2 * cir * (cir + 1) + cip)
+    return np.where(za <= 2.0 / 3.0, belt, cap)
+
+
+def lightcone_map_pixel(nside: int, x_cross) -> np.ndarray:
+    """The map pixel of crossings at x_cross (n x 3, relative to the
+    observer), as the device finds it: the angles of vec2ang, through the
+    30-bit quantisation of the reference's update buffer
+    (lightcone_shell.h:54-71), then ang2pix_ring."""
+    x = np.asarray(x_cross, dtype=np.float64).reshape(-1, 3)
+    theta = np.arctan2(np.sqrt(x[:, 0] * x[:, 0] + x[:, 1] * x[:, 1]), x[:, 2])
+    phi = np.arctan2(x[:, 1], x[:, 0])
+    phi = np.where(phi < 0.0, phi + 2.0 * np.pi, phi)
+    steps = (1 << 30) - 1
+    to_int, to_angle = steps / np.pi, np.pi / steps
+    tq = np.trunc(theta * to_int).astype(np.int64) * to_angle
+    pq = np.trunc(phi * to_int).astype(np.int64) * to_angle
+    return ang2pix_ring(nside, tq, pq)
+
+
+def lightcone_map_shells(cosmo: Cosmology, z_edges=None, r_edges=None,
+                         speed_of_light: float = 1.0) -> tuple:
+    """(r_min, r_max) of the concentric shells between consecutive edges, for
+    GravSpace.lightcone_maps_open: shell s holds r_min[s] <= r < r_max[s].
+    z_edges: redshifts (the comoving distance of each is taken; the
+    reference's shells are amin < a <= amax, the same sets); r_edges:
+    comoving distances as they are. The edges are put in ascending distance."""
+    if (z_edges is None) == (r_edges is None):
+        raise ValueError("give z_edges or r_edges")
+    if r_edges is None:
+        z = np.asarray(z_edges, dtype=np.float64).reshape(-1)
+        if np.any(z < 0.0):
+            raise ValueError("a shell edge lies at z < 0")
+        r = np.array([comoving_distance(cosmo, 1.0 / (1.0 + float(q)), speed_of_light)
+                      for q in z])
+    else:
+        r = np.asarray(r_edges, dtype=np.float64).reshape(-1)
+    r = np.sort(r)
+    if len(r) < 2 or r[0] < 0.0 or not np.all(np.isfinite(r)) or np.any(np.diff(r) <= 0.0):
+        raise ValueError("shell edges: at least two distinct, finite, non-negative values")
+    return r[:-1].copy(), r[1:].copy()
+
+
 def first_dm_mass(gparts: np.ndarray) -> float:
     """The mass of the first dark-matter gpart (type 1) that is neither
     inhibited nor not yet created (fof.c:264-274); 0 when there is none."""

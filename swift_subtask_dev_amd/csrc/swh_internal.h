@@ -87,6 +87,10 @@ struct PowerState;
 // the two record buffers, the sort's scratch, the pinned copy of the counters.
 struct LightconeState;
 
+// The HEALPix maps of a gspace's lightcone shells (swh_lightcone.hip): the
+// pixel arrays from open to close, the update counts, the pinned counters.
+struct LightconeMapState;
+
 // The hipFFT plans of the PM mesh (swh_mesh.hip).
 struct MeshPlans;
 
@@ -371,6 +375,7 @@ struct swh_gspace {
   swh::Owned<swh::FofState> fof{nullptr, nullptr};  // swh_gspace_fof (swh_fof.hip)
   swh::Owned<swh::PowerState> power{nullptr, nullptr};  // swh_gspace_power_spectrum
   swh::Owned<swh::LightconeState> lightcone{nullptr, nullptr};  // swh_gspace_lightcone_crossings
+  swh::Owned<swh::LightconeMapState> lightcone_maps{nullptr, nullptr};  // .._lightcone_maps_open
 };
 
 namespace swh {

@@ -343,7 +343,8 @@ class _GravityDriver:
 
     # -- lightcones ---------------------------------------------------------
     def add_lightcone(self, observer, speed_of_light: float, z_range=None, a_range=None,
-                      use_types=tuple(range(abi.LIGHTCONE_TYPES)), z_range_for_type=None) -> int:
+                      use_types=tuple(range(abi.LIGHTCONE_TYPES)), z_range_for_type=None,
+                      maps=None, records: bool = True) -> int:
         """Register a lightcone (src/lightcone/): from the next drift on, the
         gparts' crossings of the past light cone of `observer` are found on the
         device immediately before every gpart drift, with that drift's ti_old,
@@ -359,7 +360,18 @@ class _GravityDriver:
         the gas gparts are tested like every other type: at that point their x
         and v_full are the gas's pre-drift values (x pushed after the last
         drift, v_full after the last kick1). Nothing of the run is changed: a
-        run with lightcones equals one without bit for bit. Returns i."""
+        run with lightcones equals one without bit for bit. Returns i.
+
+        maps: dict(nside=, shell_redshifts= or shell_radii=, names=("TotalMass",
+        ...)): HEALPix mass maps of the concentric shells between consecutive
+        edges (lightcone_buffer_map_update), opened on the device at init_step
+        and added to by one more pass before every gpart drift; names are
+        those of abi.LIGHTCONE_MAP_MASKS, and a map takes every crossing of
+        its types whatever use_types and z_range_for_type say. The map pass is
+        only queued; lightcone_maps(i) fetches the maps. A gspace holds one set
+        of maps, so one lightcone of a driver may have them. records=False
+        leaves the record pass out (no record buffer is allocated; "steps"
+        stays empty)."""
         if self.cosmology is None:
             raise ValueError("add_lightcone needs a cosmology (the comoving distance of a step)")
         if not self.periodic:
@@ -379,11 +391,57 @@ class _GravityDriver:
             r_lo = cosmo_mod.comoving_distance(self.cosmology, 1.0 / (1.0 + z0), c)
             r_hi = cosmo_mod.comoving_distance(self.cosmology, 1.0 / (1.0 + z1), c)
             r2[int(t)] = (r_lo * r_lo, r_hi * r_hi)
+        if maps is None and not records:
+            raise ValueError("a lightcone without records needs maps")
+        if maps is not None:
+            if any(lc["maps"] is not None for lc in self.lightcones):
+                raise ValueError("one lightcone of a driver may have maps (a gspace holds one set)")
+            nside = maps.get("nside")
+            if nside is None or not 1 <= int(nside) <= abi.LIGHTCONE_MAX_NSIDE:
+                raise ValueError(f"maps: nside = {nside} must lie in "
+                                 f"[1, {abi.LIGHTCONE_MAX_NSIDE}]")
+            names = tuple(maps.get("names", ("TotalMass",)))
+            unknown = [m for m in names if m not in abi.LIGHTCONE_MAP_MASKS]
+            if unknown or not names or len(names) > abi.LIGHTCONE_MAX_MAPS:
+                raise ValueError(f"maps: names {names} (known: {sorted(abi.LIGHTCONE_MAP_MASKS)}, "
+                                 f"at most {abi.LIGHTCONE_MAX_MAPS})")
+            r_min, r_max = cosmo_mod.lightcone_map_shells(
+                self.cosmology, z_edges=maps.get("shell_redshifts"),
+                r_edges=maps.get("shell_radii"), speed_of_light=c)
+            maps = {"nside": int(nside), "names": names, "r_min": r_min, "r_max": r_max,
+                    "open": False, "passes": 0}
         self.lightcones.append({"observer": tuple(float(o) for o in observer), "a_min": a_min,
                                 "a_max": a_max, "speed_of_light": c,
                                 "use_types": tuple(int(t) for t in use_types), "r2_range": r2,
-                                "capacity": 0, "steps": [], "n_crossings": 0, "passes": 0})
+                                "capacity": 0, "steps": [], "n_crossings": 0, "passes": 0,
+                                "maps": maps, "records": bool(records)})
         return len(self.lightcones) - 1
+
+    def _open_lightcone_maps(self):
+        """The map set of the lightcone that has one, zeroed on the device."""
+        for lc in self.lightcones:
+            m = lc["maps"]
+            if m is not None and not m["open"]:
+                self.gs.lightcone_maps_open(m["nside"], m["r_min"], m["r_max"], m["names"])
+                m["open"] = True
+
+    def lightcone_maps(self, i: int) -> dict:
+        """The maps of lightcone i as they stand (valid wherever
+        collect_statistics is): {"maps": {shell: {name: 12 nside^2 doubles in
+        RING order}}, "updates": the adds per (shell, map) since init_step,
+        "r_min", "r_max", "names", and the counts of the last pass}. Waits for
+        the queued passes."""
+        lc = self.lightcones[i]
+        m = lc["maps"]
+        if m is None:
+            raise ValueError(f"lightcone {i} has no maps")
+        self._open_lightcone_maps()
+        res = self.gs.lightcone_maps_result()
+        out = {"names": m["names"], "r_min": m["r_min"].copy(), "r_max": m["r_max"].copy(),
+               "nside": m["nside"], "passes": m["passes"], **res}
+        out["maps"] = {s: {name: self.gs.lightcone_maps_read(s, k)
+                           for k, name in enumerate(m["names"])} for s in range(len(m["r_min"]))}
+        return out
 
     def _lightcone_passes(self, ti_old: int, ti_new: int, dt_drift: float):
         """Every registered lightcone's pass over the gparts as they are, for
@@ -395,6 +453,14 @@ class _GravityDriver:
             sh = cosmo_mod.lightcone_shell(self.cosmology, ti_old, ti_new, lc["observer"],
                                            self.box, lc["a_min"], lc["a_max"], c)
             reps = sh["replications"]
+            if lc["maps"] is not None and len(reps) > 0 and n > 0:
+                # only queued; a bad f shows in lightcone_maps(i)["n_bad_f"]
+                self._open_lightcone_maps()
+                self.gs.lightcone_maps_accumulate(abi.LightconeParams(
+                    lc["observer"], sh["R_start"], sh["R_end"], dt_drift, (self.box,) * 3, 1, reps))
+                lc["maps"]["passes"] += 1
+            if not lc["records"]:
+                continue
             if len(reps) == 0 or n == 0:
                 lc["steps"].append((ti_old, ti_new, np.zeros(0, dtype=LIGHTCONE_DTYPE)))
                 continue
@@ -429,6 +495,11 @@ class _GravityDriver:
         self._rms_pending = False
         self.GT.dt_max_RMS_displacement = self.dt_max_rms
         self.T.dt_max_RMS_displacement = self.dt_max_rms  # (the gas's; NBody: GT again)
+        for lc in self.lightcones:
+            if lc["maps"] is not None:
+                lc["maps"]["open"] = False  # a new run: the maps start from zero
+                lc["maps"]["passes"] = 0
+        self._open_lightcone_maps()
         self._drift_gparts(0, 0)
 
     # -- the RMS-displacement constraint ----------------------------------

@@ -80,6 +80,9 @@ HIP_SYMBOLS = [
     "swh_gspace_power_spectrum_times",
     "swh_gspace_lightcone_crossings", "swh_gspace_lightcone_result",
     "swh_gspace_lightcone_records", "swh_gspace_lightcone_times",
+    "swh_gspace_lightcone_maps_open", "swh_gspace_lightcone_maps_accumulate",
+    "swh_gspace_lightcone_maps_result", "swh_gspace_lightcone_maps_read",
+    "swh_gspace_lightcone_maps_times", "swh_gspace_lightcone_maps_close",
 ]
 ADAPTER_SYMBOLS = [
     "swifthip_swift_init", "swifthip_swift_finalize", "swifthip_swift_last_error",
@@ -273,6 +276,12 @@ def load(kernel: str = "cubic-spline") -> C.CDLL:
         "swh_gspace_lightcone_result": (C.c_int, [vp, P(abi.LightconeResult)]),
         "swh_gspace_lightcone_records": (C.c_int, [vp, vp, i64]),
         "swh_gspace_lightcone_times": (C.c_int, [vp, P(C.c_float)]),
+        "swh_gspace_lightcone_maps_open": (C.c_int, [vp, i32, i32, vp, vp, i32, vp]),
+        "swh_gspace_lightcone_maps_accumulate": (C.c_int, [vp, P(abi.LightconeParams)]),
+        "swh_gspace_lightcone_maps_result": (C.c_int, [vp, P(abi.LightconeMapsResult), vp]),
+        "swh_gspace_lightcone_maps_read": (C.c_int, [vp, i32, i32, vp]),
+        "swh_gspace_lightcone_maps_times": (C.c_int, [vp, P(C.c_float)]),
+        "swh_gspace_lightcone_maps_close": (C.c_int, [vp]),
     }
     missing = [name for name in sigs if not hasattr(lib, name)]
     if missing:
@@ -1240,6 +1249,64 @@ class GravSpace:
         _check(self._lib.swh_gspace_lightcone_times(self.handle, ms), "gspace_lightcone_times",
                self._lib)
         return dict(zip(abi.LIGHTCONE_STAGES, map(float, ms)))
+
+    # ---- HEALPix maps of lightcone shells (swh_lightcone.hip) --------------
+    def lightcone_maps_open(self, nside: int, r_min, r_max, maps=("TotalMass",)):
+        """Allocate zeroed maps on the device: one per (shell, map), 12 nside^2
+        doubles each, kept until lightcone_maps_close, close() or the next
+        open. r_min, r_max: the shells' comoving distance ranges; maps: names
+        of abi.LIGHTCONE_MAP_MASKS or 7-bit type masks."""
+        r_min = np.ascontiguousarray(r_min, dtype=np.float64).reshape(-1)
+        r_max = np.ascontiguousarray(r_max, dtype=np.float64).reshape(-1)
+        if len(r_min) != len(r_max):
+            raise ValueError("r_min and r_max differ in length")
+        masks = np.array([abi.LIGHTCONE_MAP_MASKS[m] if isinstance(m, str) else int(m)
+                          for m in maps], dtype=np.uint32)
+        self._lc_maps = None
+        _check(self._lib.swh_gspace_lightcone_maps_open(
+            self.handle, int(nside), len(r_min), _ptr(r_min), _ptr(r_max), len(masks),
+            _ptr(masks)), "gspace_lightcone_maps_open", self._lib)
+        self._lc_maps = (int(nside), len(r_min), len(masks))
+
+    def lightcone_maps_accumulate(self, P: abi.LightconeParams):
+        """Queue one step's crossings into the open maps (before the drift P
+        describes). P.capacity, use_type and the r2 ranges are not looked at."""
+        _check(self._lib.swh_gspace_lightcone_maps_accumulate(self.handle, C.byref(P)),
+               "gspace_lightcone_maps_accumulate", self._lib)
+
+    def lightcone_maps_result(self) -> dict:
+        """Wait for the last lightcone_maps_accumulate: its counts, and
+        "updates", the adds per (shell, map) since the open."""
+        r = abi.LightconeMapsResult()
+        shape = self._lc_maps[1:] if getattr(self, "_lc_maps", None) else (0, 0)
+        upd = np.zeros(shape, dtype=np.int64)
+        _check(self._lib.swh_gspace_lightcone_maps_result(self.handle, C.byref(r), _ptr(upd)),
+               "gspace_lightcone_maps_result", self._lib)
+        out = r.as_dict()
+        out["updates"] = upd
+        return out
+
+    def lightcone_maps_read(self, shell: int, m: int) -> np.ndarray:
+        """One map in RING order, after everything queued so far."""
+        if not getattr(self, "_lc_maps", None):
+            raise SwhError(8, "gspace_lightcone_maps_read", "no map set is open")
+        out = np.zeros(12 * self._lc_maps[0] ** 2, dtype=np.float64)
+        _check(self._lib.swh_gspace_lightcone_maps_read(self.handle, int(shell), int(m),
+                                                        _ptr(out)),
+               "gspace_lightcone_maps_read", self._lib)
+        return out
+
+    def lightcone_maps_ms(self) -> dict:
+        """HIP-event time (ms) of the last lightcone_maps_accumulate."""
+        ms = (C.c_float * 1)()
+        _check(self._lib.swh_gspace_lightcone_maps_times(self.handle, ms),
+               "gspace_lightcone_maps_times", self._lib)
+        return {"pass": float(ms[0])}
+
+    def lightcone_maps_close(self):
+        _check(self._lib.swh_gspace_lightcone_maps_close(self.handle),
+               "gspace_lightcone_maps_close", self._lib)
+        self._lc_maps = None
 
     def sync(self):
         _check(self._lib.swh_gspace_sync(self.handle), "gspace_sync", self._lib)
